@@ -325,6 +325,33 @@ class Workload:
                 "single_thread": one["value"], "all_cores": allc["value"]}
 
 
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_ROWS = 1 << 18            # rows of a per-unit output kept when all of it would not fit (a fixed, seeded sample)
+
+
+def dump_outputs(w, d):
+    """--dump-outputs DIR: what the last timed step handed its caller, one DIR/<name>.npy per array (bytes and statuses as float32 / float64,
+    exact), so that two builds run with the same arguments -- the same seeded inputs -- can be compared output for output.  -> the names written"""
+    import numpy as np
+    if w.name == "msm":
+        arrays = {"msm_status": np.array([0.0]), "msm_point": np.frombuffer(w.result["out"], np.uint8).astype(np.float64)}      # run() asserts status 0
+    elif w.name == "verify":
+        arrays = {"verify_status": np.array([float(w.result["st"])])}
+    else:
+        out = w.out.cpu().numpy()
+        key = "fixed_base_points" if w.name == "fixed_base" else "x25519_shared"
+        if out.shape[0] * out.shape[1] * 4 > DUMP_BYTES // 2:
+            rows = np.sort(np.random.default_rng(0xD0).choice(out.shape[0], size=DUMP_ROWS, replace=False))
+            arrays = {key: out[rows].astype(np.float32), key + "_rows": rows.astype(np.float64)}
+        else:
+            arrays = {key: out.astype(np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def time_steps(run, steps, warmup, barrier):
     for _ in range(warmup):
         run()
@@ -659,7 +686,11 @@ def main():
                          "are cached like the reference's VerifyingKey (verifying.rs:64-71, batch.rs:236)")
     ap.add_argument("--lib", default=os.environ.get("C25519_HIP_LIB"), help="A/B runs: another build of the library (the tuning build, a variant); the package itself reads no environment, "
                     "this HARNESS passes the choice on with an explicit select_library()")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step returned as DIR/<name>.npy (float, <= 64 MB; a seeded row sample of a larger output)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         respawn(args)
@@ -752,6 +783,8 @@ def main():
     else:
         dt = time_steps(w.run, args.steps, args.warmup, barrier)
     w.kt = w.kernel_times(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w, args.dump_outputs)
     if use_dist:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -3,6 +3,8 @@
 * two processes that share cuda:0 (gloo carries the exchange: RCCL refuses two ranks on one device), each running the
   real engine on its shard through multi.msm_vartime_sharded / multi.verify_batch_sharded -- the result must equal the
   single-context call, the oracle, and (transcript z-mode) the z_i of the ONE transcript over the whole batch;
+* the same checks with eight ranks as eight threads of one process, each with its own context on cuda:0 (no more than a few
+  processes may hold a shared GPU open at once);
 * one process with backend "nccl" and world_size 1 and force_collective=True, so that all_gather_into_tensor /
   all_reduce really execute in RCCL on device uint8 / int32 / int64 tensors;
 * bench.py launched by torch.distributed.run with --gpus 1, so that its `use_dist` branch (init_process_group("nccl"),
@@ -34,93 +36,143 @@ import curve25519_dalek_amd as pkg
 from oracle import orc
 E = pkg.engine
 L = 2**252 + 27742317777372353535851937790883648493
+dev = torch.device("cuda", 0)
+
+
+def rank_body(rank, world, eng, force):
+    """one rank's work, after its process group is up: the checks of _check as a dict"""
+    out = {"rank": rank}
+
+    # ---- MSM: the same inputs on every rank (same seed), every rank takes its shard ------------------------------------------------
+    n = int(os.environ.get("TEST_N", str((1 << 20) + 37)))
+    g = torch.Generator(device=dev); g.manual_seed(777)
+    x = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev, generator=g); x[:, 31] &= 0x0F
+    y = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev, generator=g); y[:, 31] &= 0x0F
+    pts = eng.mul_base_batch_vartime_t(y, E.FMT_RAW160)
+    lo, hi = pkg.multi.shard_range(n, rank, world)
+    st, got = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), pts[lo:hi].contiguous(), E.FMT_RAW160, E.FMT_EDWARDS_Y, force_collective=force)
+    st1, single = eng.msm_vartime_t(x, pts, E.FMT_RAW160, E.FMT_EDWARDS_Y)
+    xi = x.cpu().numpy(); yi = y.cpu().numpy()
+    acc = sum(int.from_bytes(xi[i].tobytes(), "little") * int.from_bytes(yi[i].tobytes(), "little") for i in range(n)) %% L
+    want = orc.ed_compress(orc.ed_mul_base(acc.to_bytes(32, "little")))
+    out["msm"] = (st == 0 and st1 == 0 and got == single == want)
+    # the per-step breakdown a --gpus N bench line reports (multi.StepTimes): same result, and the three parts add up to the wall-clock of the calls
+    tm = pkg.multi.StepTimes()
+    for _ in range(3):
+        st_t, got_t = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), pts[lo:hi].contiguous(), E.FMT_RAW160, E.FMT_EDWARDS_Y, force_collective=force, times=tm)
+    bm = tm.mean()
+    out["step_times"] = bm
+    out["step_times_ok"] = bool(st_t == 0 and got_t == want and bm["calls"] == 3 and all(bm[k] >= 0 for k in ("shard_ms", "collective_ms", "d2h_fold_ms"))
+                                and abs(bm["shard_ms"] + bm["collective_ms"] + bm["d2h_fold_ms"] - bm["sum_ms"]) <= 0.05 * bm["sum_ms"] and bm["shard_ms"] > 0)
+    # Ristretto / raw outputs take the same exchange
+    st, got_r = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), pts[lo:hi].contiguous(), E.FMT_RAW160, E.FMT_RISTRETTO, force_collective=force)
+    out["msm_ristretto"] = (st == 0 and got_r == orc.ris_compress(orc.ed_mul_base(acc.to_bytes(32, "little"))))
+    # a point that does not decode in ONE shard (the last term of the last rank) -> NONE on every rank
+    cp = eng.compress_batch_t(pts)
+    bad = cp.clone(); bad[n - 1] = torch.tensor(list((2).to_bytes(32, "little")), dtype=torch.uint8, device=dev)      # y = 2 is not on the curve
+    st_ok, got_c = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), cp[lo:hi].contiguous(), E.FMT_EDWARDS_Y, E.FMT_EDWARDS_Y, force_collective=force)
+    st_bad, got_b = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), bad[lo:hi].contiguous(), E.FMT_EDWARDS_Y, E.FMT_EDWARDS_Y, force_collective=force)
+    out["msm_compressed"] = (st_ok == 0 and got_c == want)
+    out["msm_none"] = (st_bad == E.NONE and got_b is None)
+    # an empty shard takes part in the exchange like any other
+    elo, ehi = (0, n) if rank == 0 else (n, n)
+    st, got_e = pkg.multi.msm_vartime_sharded(eng, x[elo:ehi].contiguous(), pts[elo:ehi].contiguous(), E.FMT_RAW160, E.FMT_EDWARDS_Y, force_collective=force)
+    out["msm_empty_shard"] = (st == 0 and got_e == want)
+
+    # ---- verify_batch: both z-modes, honest and forged, against the single-context verdict --------------------------------------
+    m = int(os.environ.get("TEST_M", "6001"))
+    seeds = torch.randint(0, 256, (m, 32), dtype=torch.uint8, device=dev, generator=g)
+    msgs = torch.randint(0, 256, (m * 24,), dtype=torch.uint8, device=dev, generator=g)
+    off = torch.arange(0, 24 * (m + 1), 24, dtype=torch.int64, device=dev)
+    pks, sigs = eng.sign_batch_t(seeds, msgs, off)
+    lo, hi = pkg.multi.shard_range(m, rank, world)
+    def shard(sg):
+        return (msgs[24 * lo:24 * hi].contiguous(), (off[lo:hi + 1] - off[lo]).contiguous(), sg[lo:hi].contiguous(), pks[lo:hi].contiguous())
+    res = {}
+    for z_mode in (E.Z_TRANSCRIPT, E.Z_DEVICE):
+        r = []
+        forged = sigs.clone(); forged[m - 3, 7] ^= 4                 # R of a signature in the last shard
+        noncanon = forged.clone(); noncanon[2, 63] |= 0xE0            # and a non-canonical s in the first shard: ScalarFormat wins
+        for sg in (sigs, forged, noncanon):
+            v = pkg.multi.verify_batch_sharded(eng, *shard(sg), z_mode=z_mode, force_collective=force)
+            v1 = eng.verify_batch_t(msgs, off, sg, pks, z_mode)
+            r.append((v, v1))
+        res[z_mode] = r
+    out["verify"] = res
+    # transcript z-mode: the z_i every rank derived are the z_i of ONE transcript over the whole batch = the single-context
+    # engine's = the oracle's, byte for byte
+    hram_t = eng.batch_hram_t(*shard(sigs)[:2], shard(sigs)[2], shard(sigs)[3])
+    hram_all, sigs_all, mylo = pkg.multi.gather_transcript_inputs(hram_t, shard(sigs)[2], force_collective=force)
+    z_all = E.batch_transcript_zs(hram_all, sigs_all)
+    mh = msgs.cpu().numpy().reshape(m, 24); sh = sigs.cpu().numpy(); ph = pks.cpu().numpy()
+    M = [mh[i].tobytes() for i in range(m)]; S = [sh[i].tobytes() for i in range(m)]; P = [ph[i].tobytes() for i in range(m)]
+    hr = [hashlib.sha512(S[i][:32] + P[i] + M[i]).digest() for i in range(m)]
+    z_orc = b"".join(orc.batch_transcript_zs(hr, [s[32:] for s in S]))
+    limit = 3 << (int(os.environ.get("C25519_VERIFY_PASS_LOG2", "20")) - 1)       # c25519_debug_batch_zs serves one pass
+    z_single = eng.debug_batch_zs(M, S, P, E.Z_TRANSCRIPT).tobytes() if m <= limit else z_orc
+    out["one_transcript"] = (mylo == lo and z_all.tobytes() == z_single == z_orc)
+    out["verdict_collective"] = [pkg.multi.combine_verdicts(v, device=dev, force_collective=force) for v in (0, 3, 2, 1)]
+    return out
+'''
+
+# one rank per process (the backend from TEST_BACKEND)
+_PROCESS_MAIN = r'''
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 torch.cuda.set_device(0)
-dev = torch.device("cuda", 0)
 dist.init_process_group(os.environ["TEST_BACKEND"], rank=rank, world_size=world, **({"device_id": dev} if os.environ["TEST_BACKEND"] == "nccl" else {}))
-force = os.environ.get("TEST_FORCE", "0") == "1"
-eng = pkg.Engine(0)
-out = {"rank": rank}
-
-# ---- MSM: the same inputs on every rank (same seed), every rank takes its shard ------------------------------------------------
-n = int(os.environ.get("TEST_N", str((1 << 20) + 37)))
-g = torch.Generator(device=dev); g.manual_seed(777)
-x = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev, generator=g); x[:, 31] &= 0x0F
-y = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device=dev, generator=g); y[:, 31] &= 0x0F
-pts = eng.mul_base_batch_vartime_t(y, E.FMT_RAW160)
-lo, hi = pkg.multi.shard_range(n, rank, world)
-st, got = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), pts[lo:hi].contiguous(), E.FMT_RAW160, E.FMT_EDWARDS_Y, force_collective=force)
-st1, single = eng.msm_vartime_t(x, pts, E.FMT_RAW160, E.FMT_EDWARDS_Y)
-xi = x.cpu().numpy(); yi = y.cpu().numpy()
-acc = sum(int.from_bytes(xi[i].tobytes(), "little") * int.from_bytes(yi[i].tobytes(), "little") for i in range(n)) %% L
-want = orc.ed_compress(orc.ed_mul_base(acc.to_bytes(32, "little")))
-out["msm"] = (st == 0 and st1 == 0 and got == single == want)
-# the per-step breakdown a --gpus N bench line reports (multi.StepTimes): same result, and the three parts add up to the wall-clock of the calls
-tm = pkg.multi.StepTimes()
-for _ in range(3):
-    st_t, got_t = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), pts[lo:hi].contiguous(), E.FMT_RAW160, E.FMT_EDWARDS_Y, force_collective=force, times=tm)
-bm = tm.mean()
-out["step_times"] = bm
-out["step_times_ok"] = bool(st_t == 0 and got_t == want and bm["calls"] == 3 and all(bm[k] >= 0 for k in ("shard_ms", "collective_ms", "d2h_fold_ms"))
-                            and abs(bm["shard_ms"] + bm["collective_ms"] + bm["d2h_fold_ms"] - bm["sum_ms"]) <= 0.05 * bm["sum_ms"] and bm["shard_ms"] > 0)
-# Ristretto / raw outputs take the same exchange
-st, got_r = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), pts[lo:hi].contiguous(), E.FMT_RAW160, E.FMT_RISTRETTO, force_collective=force)
-out["msm_ristretto"] = (st == 0 and got_r == orc.ris_compress(orc.ed_mul_base(acc.to_bytes(32, "little"))))
-# a point that does not decode in ONE shard (the last term of the last rank) -> NONE on every rank
-cp = eng.compress_batch_t(pts)
-bad = cp.clone(); bad[n - 1] = torch.tensor(list((2).to_bytes(32, "little")), dtype=torch.uint8, device=dev)      # y = 2 is not on the curve
-st_ok, got_c = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), cp[lo:hi].contiguous(), E.FMT_EDWARDS_Y, E.FMT_EDWARDS_Y, force_collective=force)
-st_bad, got_b = pkg.multi.msm_vartime_sharded(eng, x[lo:hi].contiguous(), bad[lo:hi].contiguous(), E.FMT_EDWARDS_Y, E.FMT_EDWARDS_Y, force_collective=force)
-out["msm_compressed"] = (st_ok == 0 and got_c == want)
-out["msm_none"] = (st_bad == E.NONE and got_b is None)
-# an empty shard takes part in the exchange like any other
-elo, ehi = (0, n) if rank == 0 else (n, n)
-st, got_e = pkg.multi.msm_vartime_sharded(eng, x[elo:ehi].contiguous(), pts[elo:ehi].contiguous(), E.FMT_RAW160, E.FMT_EDWARDS_Y, force_collective=force)
-out["msm_empty_shard"] = (st == 0 and got_e == want)
-
-# ---- verify_batch: both z-modes, honest and forged, against the single-context verdict --------------------------------------
-m = int(os.environ.get("TEST_M", "6001"))
-seeds = torch.randint(0, 256, (m, 32), dtype=torch.uint8, device=dev, generator=g)
-msgs = torch.randint(0, 256, (m * 24,), dtype=torch.uint8, device=dev, generator=g)
-off = torch.arange(0, 24 * (m + 1), 24, dtype=torch.int64, device=dev)
-pks, sigs = eng.sign_batch_t(seeds, msgs, off)
-lo, hi = pkg.multi.shard_range(m, rank, world)
-def shard(sg):
-    return (msgs[24 * lo:24 * hi].contiguous(), (off[lo:hi + 1] - off[lo]).contiguous(), sg[lo:hi].contiguous(), pks[lo:hi].contiguous())
-res = {}
-for z_mode in (E.Z_TRANSCRIPT, E.Z_DEVICE):
-    r = []
-    forged = sigs.clone(); forged[m - 3, 7] ^= 4                 # R of a signature in the last shard
-    noncanon = forged.clone(); noncanon[2, 63] |= 0xE0            # and a non-canonical s in the first shard: ScalarFormat wins
-    for sg in (sigs, forged, noncanon):
-        v = pkg.multi.verify_batch_sharded(eng, *shard(sg), z_mode=z_mode, force_collective=force)
-        v1 = eng.verify_batch_t(msgs, off, sg, pks, z_mode)
-        r.append((v, v1))
-    res[z_mode] = r
-out["verify"] = res
-# transcript z-mode: the z_i every rank derived are the z_i of ONE transcript over the whole batch = the single-context
-# engine's = the oracle's, byte for byte
-hram_t = eng.batch_hram_t(*shard(sigs)[:2], shard(sigs)[2], shard(sigs)[3])
-hram_all, sigs_all, mylo = pkg.multi.gather_transcript_inputs(hram_t, shard(sigs)[2], force_collective=force)
-z_all = E.batch_transcript_zs(hram_all, sigs_all)
-mh = msgs.cpu().numpy().reshape(m, 24); sh = sigs.cpu().numpy(); ph = pks.cpu().numpy()
-M = [mh[i].tobytes() for i in range(m)]; S = [sh[i].tobytes() for i in range(m)]; P = [ph[i].tobytes() for i in range(m)]
-hr = [hashlib.sha512(S[i][:32] + P[i] + M[i]).digest() for i in range(m)]
-z_orc = b"".join(orc.batch_transcript_zs(hr, [s[32:] for s in S]))
-limit = 3 << (int(os.environ.get("C25519_VERIFY_PASS_LOG2", "20")) - 1)       # c25519_debug_batch_zs serves one pass
-z_single = eng.debug_batch_zs(M, S, P, E.Z_TRANSCRIPT).tobytes() if m <= limit else z_orc
-out["one_transcript"] = (mylo == lo and z_all.tobytes() == z_single == z_orc)
-out["verdict_collective"] = [pkg.multi.combine_verdicts(v, device=dev, force_collective=force) for v in (0, 3, 2, 1)]
+out = rank_body(rank, world, pkg.Engine(0), os.environ.get("TEST_FORCE", "0") == "1")
 print("RESULT " + json.dumps(out))
 dist.barrier()
 dist.destroy_process_group()
 '''
 
+# WORLD_SIZE ranks as threads of ONE process, each with its own Engine (context) on cuda:0 -- the library's one-context-per-host-thread
+# mode (include/c25519_hip.h, c25519_msm_vartime_multi) -- over torch's thread-local "threaded" process group, which exchanges host
+# tensors like gloo (multi.py takes the same non-nccl path).  Only one process opens the GPU however many ranks there are.
+_THREADS_MAIN = r'''
+import threading, time
+from torch.testing._internal.distributed.multi_threaded_pg import _install_threaded_pg
+world = int(os.environ["WORLD_SIZE"])
+_install_threaded_pg()
+# the threaded group keeps torch's group bookkeeping per thread, but init_process_group also enters every group into one process-wide
+# by-name registry, where the eight default groups (all named "0") collide; only functional collectives resolve groups by name, and
+# multi.py uses none
+dist.distributed_c10d._register_process_group = lambda name, pg: None
+store = dist.HashStore()
+outs, errs = [None] * world, []
+
+
+def run(rank):
+    try:
+        torch.cuda.set_device(0)
+        dist.init_process_group("threaded", rank=rank, world_size=world, store=store)
+        outs[rank] = rank_body(rank, world, pkg.Engine(0), False)
+        dist.barrier()
+        dist.destroy_process_group()
+    except BaseException:
+        import traceback
+        errs.append(traceback.format_exc())
+        raise
+
+
+ts = [threading.Thread(target=run, args=(r,), daemon=True) for r in range(world)]
+for t in ts:
+    t.start()
+while any(t.is_alive() for t in ts) and not errs:          # a rank that fails leaves the others waiting in a collective: stop at once
+    time.sleep(0.05)
+if errs:
+    sys.stderr.write(errs[0]); sys.stderr.flush()
+    os._exit(1)
+for out in outs:
+    print("RESULT " + json.dumps(out))
+'''
+
 
 def _launch(world, backend, force, extra_env=None, timeout=900):
+    """world ranks, one process each"""
     port = _free_port()
     procs = []
-    code = _COMMON % {"root": ROOT}
+    code = _COMMON % {"root": ROOT} + _PROCESS_MAIN
     for r in range(world):
         env = dict(os.environ)
         env.update({"RANK": str(r), "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "TEST_BACKEND": backend,
@@ -143,6 +195,17 @@ def _launch(world, backend, force, extra_env=None, timeout=900):
         outs.append(json.loads(line[-1][7:]))
     return outs
 
+
+
+def _launch_threads(world, extra_env=None, timeout=900):
+    """world ranks as threads of one child process (the GPU is opened by that process alone)"""
+    env = dict(os.environ, WORLD_SIZE=str(world))
+    env.update(extra_env or {})
+    r = subprocess.run(util.child_argv(_COMMON % {"root": ROOT} + _THREADS_MAIN), env=env, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    outs = [json.loads(ln[7:]) for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+    assert len(outs) == world, (r.stdout[-2000:], r.stderr[-2000:])
+    return outs
 
 def _check(outs):
     OK, NONE, SCALAR_FORMAT, VERIFY = 0, 1, 2, 3
@@ -173,11 +236,12 @@ def test_three_ranks_many_passes_gloo():
 
 @pytest.mark.parametrize("n,m", [(1003, 77), (5, 5)])
 def test_eight_ranks_on_one_gpu_real_engine_gloo(n, m):
-    """world_size 8 -- the size BASELINE configs[3] is quoted on -- with the real engine on every rank, all sharing cuda:0 over gloo:
+    """world_size 8 -- the size BASELINE configs[3] is quoted on -- with the real engine on every rank, all sharing cuda:0 (eight threads of one
+    process, _THREADS_MAIN: eight processes with the GPU open is more than a shared box allows), the host exchange of the gloo path:
     the index arithmetic of multi.shard_range / gather_transcript_inputs / the record fold at eight ranks.  (1003, 77): tiny RAGGED shards
     (125 / 126 terms, 9 / 10 signatures), the undecodable point on the last rank (NONE everywhere), seven EMPTY shards beside one full one;
     (5, 5): more ranks than units -- ranks 5..7 hold nothing in the MSM, in both verify_batch z-modes and in the ONE transcript."""
-    outs = _launch(8, "gloo", False, {"TEST_N": str(n), "TEST_M": str(m)})
+    outs = _launch_threads(8, {"TEST_N": str(n), "TEST_M": str(m)})
     assert sorted(o["rank"] for o in outs) == list(range(8))
     _check(outs)
 
