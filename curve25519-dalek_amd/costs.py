@@ -16,6 +16,10 @@ Formula sources (file:function):
   decompression                 255 S + 21 M                             ge26.h:ge_decompress (T = X*Y is dead code in the MSM prep)
   batched compression           5 M + inversion / 16                     finish.hip:k_compress_p32<16>
   affine Niels record           2 M (x*y, *2d)                           devio.h:pts_store
+  sqrt_ratio_i                  254 S + 20 M                             ge26.h:fe_sqrt_ratio_i (pow_p58 + 8 M + 3 S around it)
+  Ristretto Elligator map       256 S + 33 M                             h2c.h:ris_elligator
+  Ristretto compression         255 S + 33 M                             ge26.h:ris_compress
+  Elligator 2 + Edwards map     258 S + 36 M                             h2c.h:mont_elligator2 + ed_h2c_map
 """
 import math
 
@@ -114,12 +118,35 @@ def verify(n, nwin, half, keys_as_bytes=False, r_windows=8):
     return c
 
 
+SQRT_RATIO = {"M": 20, "S": 254}
+RIS_MAP = _add(SQRT_RATIO, {"M": 13, "S": 2})       # r = i r0^2 (1 S + 1 M), N_s, D (3 M), s' (1 M), N_t (2 M), s^2 (1 S), W (2 M), to extended (4 M)
+RIS_COMPRESS = _add(SQRT_RATIO, {"M": 13, "S": 1})
+ED_MAP = _add({"M": 12, "S": 251}, {"M": 24, "S": 7})  # pow_p58 of G.2.1 step 16 + the other 17 M + 7 S of G.2.1 + 7 M of the rational map
+ADD = {"M": 9, "S": 0}
+
+
+def ristretto_from_uniform(compressed=True):
+    """h2c.hip:k_ristretto_from_uniform: two Elligator maps (three exponentiation chains with the compression), the sum."""
+    c = _add(RIS_MAP, RIS_MAP, ADD, RIS_COMPRESS if compressed else {"M": 0, "S": 0})
+    c["what"] = "2 Elligator maps (256 S + 33 M each) + 9 M sum" + (" + Ristretto compression (255 S + 33 M)" if compressed else " (RAW160 out)")
+    return c
+
+
+def edwards_hash_to_curve(ro=True):
+    """h2c.hip:k_edwards_h2c<RO> + the batched compression; SHA-512 (4 compressions of expand_message_xmd for a short message, RO) is
+    integer work outside this count."""
+    c = _add(ED_MAP, ED_MAP if ro else {"M": 0, "S": 0}, ADD if ro else {"M": 0, "S": 0}, {"M": 10, "S": 12}, compress_batch())
+    c["what"] = "%s Elligator 2 + Edwards map (258 S + 36 M)%s + x8 (12 S + 10 M) + 5 M compress + 1/16 inversion" % ("2 x" if ro else "1 x", " + 9 M sum" if ro else "")
+    return c
+
+
 def table():
     """Rows for DESIGN.md (python -m curve25519_dalek_amd.costs)."""
     rows = [("fixed base, radix 2^16 tables", fixed_base_wide(16)), ("fixed base, LDS comb", fixed_base_comb()),
             ("fixed base, constant-time scan W=5", fixed_base_ct(5)), ("X25519 ladder", x25519()),
             ("MSM 2^21 terms, raw points", msm(1 << 21, 17, 32768)), ("verify_batch 2^20, VerifyingKey", verify(1 << 20, 17, 32768)),
-            ("verify_batch 2^20, keys as bytes", verify(1 << 20, 17, 32768, True))]
+            ("verify_batch 2^20, keys as bytes", verify(1 << 20, 17, 32768, True)),
+            ("Ristretto from_uniform_bytes", ristretto_from_uniform()), ("Edwards hash_to_curve (RO)", edwards_hash_to_curve())]
     return [(name, round(c["M"], 1), round(c["S"], 1), int(round(mac(c))), c["what"]) for name, c in rows]
 
 

@@ -18,6 +18,8 @@ error behaviour), batched, on top of Engine.  Reference entry points mirrored:
   RistrettoBasepointTable::create             curve25519-dalek/src/ristretto.rs:1080-1110
   EdwardsPoint::mul_base_clamped / mul_clamped   curve25519-dalek/src/edwards.rs:948 / :932
   SharedSecret::was_contributory              x25519-dalek/src/x25519.rs:335
+  RistrettoPoint::from_uniform_bytes / map_to_curve / hash_from_bytes::<Sha512>   ristretto.rs:774 / elligator.rs:62 / ristretto.rs:736
+  EdwardsPoint::hash_to_curve / encode_to_curve::<Sha512>   curve25519-dalek/src/edwards.rs:710-750 (RFC 9380)
   EdwardsPoint::is_small_order / is_torsion_free   curve25519-dalek/src/edwards.rs:1405 / :1435;  VerifyingKey::is_weak  ed25519-dalek/src/verifying.rs:192
 
 Values cross this layer as the reference's wire types: Scalar = 32 canonical LE bytes,
@@ -26,6 +28,18 @@ CompressedEdwardsY / CompressedRistretto / MontgomeryPoint = 32 bytes.
 import numpy as np
 
 from . import engine as _e
+
+
+class DomainSeparatorError(ValueError):
+    """hash_to_curve / encode_to_curve with an empty domain separator or one longer than 255 bytes (a panic in the reference,
+    field.rs:457-462)"""
+
+
+def _joined(x):
+    """bytes, or a sequence of byte pieces concatenated -- the reference's `&[&[u8]]`"""
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        return bytes(x)
+    return b"".join(bytes(p) for p in x)
 
 
 class SignatureError(Exception):
@@ -50,6 +64,15 @@ def _cat(items, width):
     if len(items) == 0:
         return np.zeros((0, width), dtype=np.uint8)
     return np.frombuffer(b"".join(bytes(x) for x in items), dtype=np.uint8).reshape(-1, width)
+
+
+def _edwards_h2c(messages, domain_sep, mode, engine):
+    dst = _joined(domain_sep)
+    if not 0 < len(dst) <= 255:
+        raise DomainSeparatorError("domain separator must have 1 .. 255 bytes, got %d" % len(dst))
+    eng = engine or default_engine()
+    out = eng.edwards_hash_to_curve_batch([_joined(m) for m in messages], dst, mode, _e.FMT_EDWARDS_Y)
+    return [out[i].tobytes() for i in range(out.shape[0])]
 
 
 class EdwardsPoint:
@@ -97,6 +120,18 @@ class EdwardsPoint:
         eng = engine or default_engine()
         out, ok = eng.mul_clamped_batch(_cat(raw_bytes, 32), _cat(points, 32), _e.FMT_EDWARDS_Y, _e.FMT_EDWARDS_Y)
         return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+    @staticmethod
+    def hash_to_curve(messages, domain_sep, engine=None):
+        """[EdwardsPoint::hash_to_curve::<Sha512>(msg_i, domain_sep)] as CompressedEdwardsY bytes (edwards.rs:736-750, RFC 9380
+        edwards25519_XMD:SHA-512_ELL2_RO_).  Each message and the DST: bytes, or a list of pieces concatenated (the reference's
+        &[&[u8]]).  An empty DST or one longer than 255 bytes raises DomainSeparatorError (the reference panics)."""
+        return _edwards_h2c(messages, domain_sep, _e.H2C_RO, engine)
+
+    @staticmethod
+    def encode_to_curve(messages, domain_sep, engine=None):
+        """[EdwardsPoint::encode_to_curve::<Sha512>(msg_i, domain_sep)] (edwards.rs:710-734, ..._ELL2_NU_), arguments as hash_to_curve"""
+        return _edwards_h2c(messages, domain_sep, _e.H2C_NU, engine)
 
 
 def _order_flags(points, which, engine):
@@ -158,6 +193,36 @@ class RistrettoPoint:
         eng = engine or default_engine()
         st, out = eng.msm_vartime(_cat(scalars, 32), _cat(points, 32), _e.FMT_RISTRETTO, _e.FMT_RISTRETTO)
         return None if st == _e.NONE else out
+
+
+    @staticmethod
+    def from_uniform_bytes(inputs, engine=None):
+        """[RistrettoPoint::from_uniform_bytes(b_i).compress()] for 64-byte inputs (ristretto.rs:774)"""
+        _check_width(inputs, 64, "from_uniform_bytes")
+        eng = engine or default_engine()
+        out = eng.ristretto_from_uniform_bytes_batch(_cat(inputs, 64), _e.FMT_RISTRETTO)
+        return [out[i].tobytes() for i in range(out.shape[0])]
+
+    @staticmethod
+    def map_to_curve(inputs, engine=None):
+        """[RistrettoPoint::map_to_curve(b_i).compress()] for 32-byte inputs (ristretto/elligator.rs:62-68: bit 255 ignored)"""
+        _check_width(inputs, 32, "map_to_curve")
+        eng = engine or default_engine()
+        out = eng.ristretto_map_to_curve_batch(_cat(inputs, 32), _e.FMT_RISTRETTO)
+        return [out[i].tobytes() for i in range(out.shape[0])]
+
+    @staticmethod
+    def hash_from_bytes(messages, engine=None):
+        """[RistrettoPoint::hash_from_bytes::<Sha512>(m_i).compress()] (ristretto.rs:736-761); a message may be a list of pieces"""
+        eng = engine or default_engine()
+        out = eng.ristretto_hash_from_bytes_batch([_joined(m) for m in messages], _e.FMT_RISTRETTO)
+        return [out[i].tobytes() for i in range(out.shape[0])]
+
+
+def _check_width(items, width, what):
+    for i, it in enumerate(items):
+        if len(it) != width:
+            raise ValueError("%s: input %d has %d bytes, expected %d" % (what, i, len(it), width))
 
 
 class CompressedEdwardsY:

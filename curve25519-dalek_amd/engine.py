@@ -10,6 +10,8 @@ import os
 import numpy as np
 
 OK, NONE, SCALAR_FORMAT, VERIFY, ARRAY_LENGTH, PREHASHED_CONTEXT_LENGTH = 0, 1, 2, 3, 4, 5
+DOMAIN_SEPARATOR_LENGTH = 6      # hash-to-curve: a DST of 0 or more than 255 bytes
+H2C_NU, H2C_RO = 0, 1            # c25519_edwards_hash_to_curve_batch mode: encode_to_curve / hash_to_curve
 FMT_EDWARDS_Y, FMT_RISTRETTO, FMT_RAW160 = 0, 1, 2
 POINT_DECODES, POINT_SMALL_ORDER, POINT_TORSION_FREE = 1, 2, 4      # flags of c25519_point_order_checks_batch
 Z_TRANSCRIPT, Z_DEVICE = 0, 1
@@ -138,6 +140,14 @@ def load_library():
         "c25519_double_and_compress_batch_dev": (i32, [vp, vp, u64, vp]),
         "c25519_double_and_compress_batch": (i32, [vp, vp, u64, vp]),
         "c25519_scalar_invert_batch": (i32, [vp, vp, u64, vp]),
+        "c25519_ristretto_from_uniform_bytes_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
+        "c25519_ristretto_from_uniform_bytes_batch": (i32, [vp, vp, u64, C.c_int, vp]),
+        "c25519_ristretto_map_to_curve_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
+        "c25519_ristretto_map_to_curve_batch": (i32, [vp, vp, u64, C.c_int, vp]),
+        "c25519_ristretto_hash_from_bytes_batch_dev": (i32, [vp, vp, vp, u64, u64, C.c_int, vp]),
+        "c25519_ristretto_hash_from_bytes_batch": (i32, [vp, vp, vp, u64, C.c_int, vp]),
+        "c25519_edwards_hash_to_curve_batch_dev": (i32, [vp, vp, vp, u64, u64, C.c_char_p, C.c_uint32, C.c_int, C.c_int, vp]),
+        "c25519_edwards_hash_to_curve_batch": (i32, [vp, vp, vp, u64, C.c_char_p, C.c_uint32, C.c_int, C.c_int, vp]),
         "c25519_microbench": (C.c_double, [vp, C.c_int, C.c_int]),
         "c25519_selftest_field": (i32, [vp, C.c_int, C.c_int, vp, vp, u64, vp]),
         "c25519_selftest_scalar": (i32, [vp, C.c_int, vp, vp, u64, vp]),
@@ -168,6 +178,9 @@ ABI_SYMBOLS = [
     "c25519_precomp_create", "c25519_precomp_destroy", "c25519_precomp_len", "c25519_precomp_msm_vartime",
     "c25519_msm_consttime", "c25519_double_and_compress_batch_dev", "c25519_double_and_compress_batch",
     "c25519_scalar_invert_batch",
+    "c25519_ristretto_from_uniform_bytes_batch_dev", "c25519_ristretto_from_uniform_bytes_batch", "c25519_ristretto_map_to_curve_batch_dev",
+    "c25519_ristretto_map_to_curve_batch", "c25519_ristretto_hash_from_bytes_batch_dev", "c25519_ristretto_hash_from_bytes_batch",
+    "c25519_edwards_hash_to_curve_batch_dev", "c25519_edwards_hash_to_curve_batch",
 ]
 
 _PT = {FMT_EDWARDS_Y: 32, FMT_RISTRETTO: 32, FMT_RAW160: 160}
@@ -463,6 +476,41 @@ class Engine:
         self._bind_stream()
         self._chk(self.lib.ed25519_sign_batch_dev(self.ctx, seeds.data_ptr(), msgs.data_ptr(), msg_off.data_ptr(), msgs.numel(), n, pks.data_ptr(), sigs.data_ptr()))
         return pks, sigs
+
+    # -- hash-to-group on device tensors: -> (n, 32) or (n, 160) uint8 tensor, or DOMAIN_SEPARATOR_LENGTH (an int) for a bad DST
+    def _h2c_out_t(self, n, out_fmt):
+        return self.torch.empty((n, _PT[out_fmt]), dtype=self.torch.uint8, device=self.device)
+
+    def ristretto_from_uniform_bytes_batch_t(self, in64, out_fmt=FMT_RISTRETTO):
+        n = self._t(in64, 64)
+        out = self._h2c_out_t(n, out_fmt)
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_from_uniform_bytes_batch_dev(self.ctx, in64.data_ptr(), n, out_fmt, out.data_ptr()))
+        return out
+
+    def ristretto_map_to_curve_batch_t(self, in32, out_fmt=FMT_RISTRETTO):
+        n = self._t(in32, 32)
+        out = self._h2c_out_t(n, out_fmt)
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_map_to_curve_batch_dev(self.ctx, in32.data_ptr(), n, out_fmt, out.data_ptr()))
+        return out
+
+    def ristretto_hash_from_bytes_batch_t(self, msgs, msg_off, out_fmt=FMT_RISTRETTO):
+        """msgs: uint8 CUDA tensor of the concatenated messages; msg_off: int64/uint64 CUDA tensor (n+1)"""
+        n = msg_off.numel() - 1
+        out = self._h2c_out_t(n, out_fmt)
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_hash_from_bytes_batch_dev(self.ctx, msgs.data_ptr(), msg_off.data_ptr(), msgs.numel(), n, out_fmt, out.data_ptr()))
+        return out
+
+    def edwards_hash_to_curve_batch_t(self, msgs, msg_off, dst, mode=H2C_RO, out_fmt=FMT_EDWARDS_Y):
+        n = msg_off.numel() - 1
+        out = self._h2c_out_t(n, out_fmt)
+        self._bind_stream()
+        dst = bytes(dst)
+        st = self._chk(self.lib.c25519_edwards_hash_to_curve_batch_dev(self.ctx, msgs.data_ptr(), msg_off.data_ptr(), msgs.numel(), n, dst, len(dst), mode, out_fmt,
+                                                                       out.data_ptr()), (OK, DOMAIN_SEPARATOR_LENGTH))
+        return out if st == OK else st
 
     # -- host-buffer API (numpy in / numpy out) ---------------------------------------------------
     @staticmethod
@@ -762,6 +810,48 @@ class Engine:
         self._bind_stream()
         self._chk(self.lib.c25519_double_and_compress_batch(self.ctx, p.ctypes.data, n, out.ctypes.data))
         return out
+
+    # -- hash-to-group, host buffers: -> numpy (n, 32) or (n, 160) uint8
+    def ristretto_from_uniform_bytes_batch(self, in64, out_fmt=FMT_RISTRETTO, out=None):
+        a = _np8(in64, 64) if len(in64) else np.empty((0, 64), np.uint8); n = a.shape[0]
+        out = self._out(out, n, _PT[out_fmt])
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_from_uniform_bytes_batch(self.ctx, a.ctypes.data, n, out_fmt, out.ctypes.data))
+        return out
+
+    def ristretto_map_to_curve_batch(self, in32, out_fmt=FMT_RISTRETTO, out=None):
+        a = _np8(in32, 32) if len(in32) else np.empty((0, 32), np.uint8); n = a.shape[0]
+        out = self._out(out, n, _PT[out_fmt])
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_map_to_curve_batch(self.ctx, a.ctypes.data, n, out_fmt, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _pack_off(msgs, msg_off):
+        """msgs: a list of byte strings, or (blob, offsets) already packed"""
+        if msg_off is None:
+            return Engine._pack(list(msgs))
+        return np.ascontiguousarray(np.frombuffer(bytes(msgs), dtype=np.uint8)), np.ascontiguousarray(msg_off, dtype=np.uint64)
+
+    def ristretto_hash_from_bytes_batch(self, msgs, out_fmt=FMT_RISTRETTO, msg_off=None, out=None):
+        blob, off = self._pack_off(msgs, msg_off)
+        n = off.shape[0] - 1
+        out = self._out(out, n, _PT[out_fmt])
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_hash_from_bytes_batch(self.ctx, blob.ctypes.data, off.ctypes.data, n, out_fmt, out.ctypes.data))
+        return out
+
+    def edwards_hash_to_curve_batch(self, msgs, dst, mode=H2C_RO, out_fmt=FMT_EDWARDS_Y, msg_off=None, out=None):
+        """RFC 9380 edwards25519_XMD:SHA-512_ELL2_RO_ (mode H2C_RO) / _NU_ (H2C_NU) with one DST for the batch.
+        -> numpy array, or DOMAIN_SEPARATOR_LENGTH (an int) when the DST is empty or longer than 255 bytes."""
+        blob, off = self._pack_off(msgs, msg_off)
+        n = off.shape[0] - 1
+        out = self._out(out, n, _PT[out_fmt])
+        dst = bytes(dst)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_edwards_hash_to_curve_batch(self.ctx, blob.ctypes.data, off.ctypes.data, n, dst, len(dst), mode, out_fmt, out.ctypes.data),
+                       (OK, DOMAIN_SEPARATOR_LENGTH))
+        return out if st == OK else st
 
     def scalar_invert_batch(self, scalars):
         """-> (inverses (n,32), product of all inverses (32 bytes)); inputs must be canonical and non-zero."""

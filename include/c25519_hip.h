@@ -49,6 +49,7 @@ extern "C" {
 #define C25519_VERIFY 3
 #define C25519_ARRAY_LENGTH 4
 #define C25519_PREHASHED_CONTEXT_LENGTH 5   /* Ed25519ph: context longer than 255 octets (errors.rs InternalError::PrehashedContextLength) */
+#define C25519_DOMAIN_SEPARATOR_LENGTH 6    /* hash-to-curve: a DST of 0 or more than 255 bytes (the reference panics, field.rs:457-462) */
 
 #define C25519_FMT_EDWARDS_Y 0
 #define C25519_FMT_RISTRETTO 1
@@ -432,6 +433,37 @@ int32_t c25519_msm_consttime(c25519_ctx *ctx, const uint8_t *scalars, const uint
  * shared inversion per lane-chunk.  in: n x 160 raw points; out: n x 32 CompressedRistretto. */
 int32_t c25519_double_and_compress_batch_dev(c25519_ctx *ctx, const uint8_t *d_in, uint64_t n, uint8_t *d_out);
 int32_t c25519_double_and_compress_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out);
+
+/* ---- hash-to-group: points from bytes, one item per lane ----------------------------------------------------------------
+ * Output formats: the Ristretto calls write C25519_FMT_RISTRETTO (n x 32) or C25519_FMT_RAW160 (n x 160, to feed
+ * c25519_msm_vartime_dev / c25519_precomp_create without a round trip); the Edwards call writes C25519_FMT_EDWARDS_Y or
+ * C25519_FMT_RAW160.  Any other out_fmt returns -(hipErrorInvalidValue).  n == 0 returns C25519_OK.
+ * from_uniform_bytes and map_to_curve are constant-time in their inputs (selects only, no branch or address depends on a byte);
+ * the hashing calls branch on message lengths only.
+ * Messages as in ed25519_verify_batch: msgs concatenated, msg_off n+1 offsets; for the _dev forms msg_off must be
+ * non-decreasing with msg_off[n] <= msgs_len, otherwise the call returns -(hipErrorInvalidValue) and no byte outside
+ * [msgs, msgs + msgs_len) is read.  The hashing _dev forms synchronise the context's stream (they read that verdict back). */
+/* RistrettoPoint::from_uniform_bytes (ristretto.rs:774): in: n x 64 bytes, two Elligator maps (ristretto/elligator.rs:15-52) and their sum. */
+int32_t c25519_ristretto_from_uniform_bytes_batch_dev(c25519_ctx *ctx, const uint8_t *d_in64, uint64_t n, int out_fmt, uint8_t *d_out);
+int32_t c25519_ristretto_from_uniform_bytes_batch(c25519_ctx *ctx, const uint8_t *in64, uint64_t n, int out_fmt, uint8_t *out);
+/* RistrettoPoint::map_to_curve (ristretto/elligator.rs:62-68, RFC 9496 MAP): in: n x 32 bytes, bit 255 ignored, values >= p reduced. */
+int32_t c25519_ristretto_map_to_curve_batch_dev(c25519_ctx *ctx, const uint8_t *d_in32, uint64_t n, int out_fmt, uint8_t *d_out);
+int32_t c25519_ristretto_map_to_curve_batch(c25519_ctx *ctx, const uint8_t *in32, uint64_t n, int out_fmt, uint8_t *out);
+/* RistrettoPoint::hash_from_bytes::<Sha512> (ristretto.rs:736-761): from_uniform_bytes(SHA-512(msg_i)). */
+int32_t c25519_ristretto_hash_from_bytes_batch_dev(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len, uint64_t n,
+                                                   int out_fmt, uint8_t *d_out);
+int32_t c25519_ristretto_hash_from_bytes_batch(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, int out_fmt, uint8_t *out);
+/* EdwardsPoint::hash_to_curve::<Sha512> (mode C25519_H2C_RO, RFC 9380 edwards25519_XMD:SHA-512_ELL2_RO_) and
+ * EdwardsPoint::encode_to_curve::<Sha512> (mode C25519_H2C_NU, ..._ELL2_NU_), edwards.rs:710-750: expand_message_xmd
+ * (field.rs:440-490), hash_to_field (field.rs:397-428), Elligator 2 (montgomery.rs:276-363) and the map to edwards25519
+ * (edwards.rs:651-690), the sum (RO), mul_by_cofactor.  dst: HOST pointer in both forms, ONE domain separator for the batch
+ * (the reference's concatenated domain_sep), 1 .. 255 bytes, else C25519_DOMAIN_SEPARATOR_LENGTH. */
+#define C25519_H2C_NU 0
+#define C25519_H2C_RO 1
+int32_t c25519_edwards_hash_to_curve_batch_dev(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len, uint64_t n,
+                                               const uint8_t *dst, uint32_t dst_len, int mode, int out_fmt, uint8_t *d_out);
+int32_t c25519_edwards_hash_to_curve_batch(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n,
+                                           const uint8_t *dst, uint32_t dst_len, int mode, int out_fmt, uint8_t *out);
 
 /* ---- Scalar::invert_batch_alloc (scalar.rs:802-856): io[i] <- 1/io[i] mod l in place (HOST pointer; all inputs
  * must be canonical and non-zero, as in the reference); prod_inv (32 bytes, may be NULL) receives the product of

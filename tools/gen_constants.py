@@ -71,6 +71,14 @@ D_MINUS_ONE_SQ = (D - 1) ** 2 % P
 
 APLUS2_OVER_FOUR = 121666
 
+# hash-to-curve (RFC 9380 Appendix G.2.1 / G.2.2): Montgomery A = J = 486662, c2 = 2^((p+3)/8) of elligator_encode, and the
+# constant of the birational map to edwards25519, sqrt(-486664) with sgn0 = 0 (the even root)
+MONT_A = 486662
+H2C_C2 = pow(2, (P + 3) // 8, P)
+SQRT_AM2 = fsqrt((-486664) % P)
+if is_neg(SQRT_AM2):
+    SQRT_AM2 = P - SQRT_AM2
+
 # scalar Montgomery constants (R = 2^260, 52-bit limbs)
 LFACTOR = (-pow(L, -1, 2**52)) % 2**52
 R = 2**260 % L
@@ -205,7 +213,14 @@ def main():
     dev = ["/* GENERATED by tools/gen_constants.py -- do not edit.",
            "   Curve constants as 10 x u32 radix-2^25.5 limbs for the gfx950 device code. */",
            "#pragma once", ""]
-    for name, val, com in fe:
+    # device-only constants (the oracle has no hash-to-curve)
+    fe_dev = [
+        ("MONTGOMERY_A", MONT_A, "Montgomery A = J = 486662 (RFC 9380 G.2.1)"),
+        ("MONTGOMERY_A_NEG", (-MONT_A) % P, "-A (x1n of RFC 9380 G.2.1)"),
+        ("H2C_C2", H2C_C2, "c2 = 2^((p+3)/8) of RFC 9380 G.2.1"),
+        ("ED25519_SQRTAM2", SQRT_AM2, "sqrt(-486664), sgn0 = 0: the birational map to edwards25519 (RFC 9380 G.2.2)"),
+    ]
+    for name, val, com in fe + fe_dev:
         dev.append(c_u32("C25519_" + name + "_26", limbs26(val), com))
     # l as 8 x u32 little-endian words, and Barrett/Montgomery helpers for the device scalar code
     dev.append("#define C25519_L_W32 { %s }" % ", ".join("0x%08xu" % ((L >> (32 * i)) & 0xffffffff) for i in range(8)))
@@ -220,6 +235,7 @@ def main():
 
     # sanity: basepoint has order l, 2B / known facts
     assert (-BX * BX + BY * BY - 1 - D * BX * BX * BY * BY) % P == 0
+    assert SQRT_AM2 * SQRT_AM2 % P == (-486664) % P and pow(H2C_C2, 4, P) == P - 4
     print("constants written")
 
 
