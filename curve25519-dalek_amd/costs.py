@@ -20,6 +20,9 @@ Formula sources (file:function):
   Ristretto Elligator map       256 S + 33 M                             h2c.h:ris_elligator
   Ristretto compression         255 S + 33 M                             ge26.h:ris_compress
   Elligator 2 + Edwards map     258 S + 36 M                             h2c.h:mont_elligator2 + ed_h2c_map
+  Ristretto decompression       257 S + 27 M                             ge26.h:ris_decompress
+  Jacobi quartic points (4)     258 S + 40 M                             lizard.h:ris_to_jacobi_quartic
+  e_inv_positive                257 S + 23 M                             lizard.h:jacobi_e_inv_positive (8 per decode / inverse)
 """
 import math
 
@@ -140,13 +143,41 @@ def edwards_hash_to_curve(ro=True):
     return c
 
 
+RIS_DECOMPRESS = _add(SQRT_RATIO, {"M": 7, "S": 3})
+JACOBI4 = _add(SQRT_RATIO, {"M": 20, "S": 4})       # 4 S of X^2 Y^2 Y^4 Z^2, 2 M into the invsqrt, 18 M of the s_i, t_i
+E_INV = _add(SQRT_RATIO, {"M": 3, "S": 3})           # a, i (s^4 - a^2), x (3 M); a^2, s^2, s^4 (3 S)
+
+
+def lizard_encode(compressed=True):
+    """lizard.hip:k_lizard_encode: one Elligator map and the compression; SHA-256 (one compression) is integer work outside this count."""
+    c = _add(RIS_MAP, RIS_COMPRESS if compressed else {"M": 0, "S": 0})
+    c["what"] = "1 Elligator map (256 S + 33 M)" + (" + Ristretto compression (255 S + 33 M)" if compressed else " (RAW160 out)")
+    return c
+
+
+def lizard_decode(compressed=True):
+    """lizard.hip:k_lizard_decode: (decompression,) the four Jacobi points, 8 e_inv_positive; 8 SHA-256 compressions are integer
+    work outside this count.  Ten inverse square roots from compressed input, nine from RAW160."""
+    c = _add(RIS_DECOMPRESS if compressed else {"M": 0, "S": 0}, JACOBI4, _scaled(E_INV, 8))
+    c["what"] = ("decompression + " if compressed else "") + "4 Jacobi points (258 S + 40 M) + 8 x e_inv_positive (257 S + 23 M)"
+    return c
+
+
+def map_to_curve_inverse(compressed=True):
+    """lizard.hip:k_map_to_curve_inverse: the field work of lizard_decode without the hashes"""
+    c = lizard_decode(compressed)
+    c["what"] = "as lizard_decode, 16 canonical encodings out instead of 8 hashes"
+    return c
+
+
 def table():
     """Rows for DESIGN.md (python -m curve25519_dalek_amd.costs)."""
     rows = [("fixed base, radix 2^16 tables", fixed_base_wide(16)), ("fixed base, LDS comb", fixed_base_comb()),
             ("fixed base, constant-time scan W=5", fixed_base_ct(5)), ("X25519 ladder", x25519()),
             ("MSM 2^21 terms, raw points", msm(1 << 21, 17, 32768)), ("verify_batch 2^20, VerifyingKey", verify(1 << 20, 17, 32768)),
             ("verify_batch 2^20, keys as bytes", verify(1 << 20, 17, 32768, True)),
-            ("Ristretto from_uniform_bytes", ristretto_from_uniform()), ("Edwards hash_to_curve (RO)", edwards_hash_to_curve())]
+            ("Ristretto from_uniform_bytes", ristretto_from_uniform()), ("Edwards hash_to_curve (RO)", edwards_hash_to_curve()),
+            ("Lizard encode", lizard_encode()), ("Lizard decode (compressed in)", lizard_decode()), ("map_to_curve_inverse", map_to_curve_inverse())]
     return [(name, round(c["M"], 1), round(c["S"], 1), int(round(mac(c))), c["what"]) for name, c in rows]
 
 

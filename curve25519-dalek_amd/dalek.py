@@ -20,6 +20,8 @@ error behaviour), batched, on top of Engine.  Reference entry points mirrored:
   SharedSecret::was_contributory              x25519-dalek/src/x25519.rs:335
   RistrettoPoint::from_uniform_bytes / map_to_curve / hash_from_bytes::<Sha512>   ristretto.rs:774 / elligator.rs:62 / ristretto.rs:736
   EdwardsPoint::hash_to_curve / encode_to_curve::<Sha512>   curve25519-dalek/src/edwards.rs:710-750 (RFC 9380)
+  RistrettoPoint::lizard_encode / lizard_decode::<Sha256>, map_to_curve_inverse, map_to_curve_restricted
+                                              curve25519-dalek/src/lizard/lizard_ristretto.rs:25 / :46 / :232 / :215 (feature `lizard`)
   EdwardsPoint::is_small_order / is_torsion_free   curve25519-dalek/src/edwards.rs:1405 / :1435;  VerifyingKey::is_weak  ed25519-dalek/src/verifying.rs:192
 
 Values cross this layer as the reference's wire types: Scalar = 32 canonical LE bytes,
@@ -217,6 +219,43 @@ class RistrettoPoint:
         eng = engine or default_engine()
         out = eng.ristretto_hash_from_bytes_batch([_joined(m) for m in messages], _e.FMT_RISTRETTO)
         return [out[i].tobytes() for i in range(out.shape[0])]
+
+    @staticmethod
+    def lizard_encode(datas, engine=None):
+        """[RistrettoPoint::lizard_encode::<Sha256>(d_i).compress()] for 16-byte payloads (lizard_ristretto.rs:25-42)"""
+        _check_width(datas, 16, "lizard_encode")
+        eng = engine or default_engine()
+        out = eng.ristretto_lizard_encode_batch(_cat(datas, 16), _e.FMT_RISTRETTO)
+        return [out[i].tobytes() for i in range(out.shape[0])]
+
+    @staticmethod
+    def lizard_decode(encodings, engine=None):
+        """[CompressedRistretto(b_i).decompress().and_then(|p| p.lizard_decode::<Sha256>())]: 16 bytes, or None for an invalid
+        encoding or a point without a unique Lizard preimage (lizard_ristretto.rs:46-75)"""
+        _check_width(encodings, 32, "lizard_decode")
+        eng = engine or default_engine()
+        out, st = eng.ristretto_lizard_decode_batch(_cat(encodings, 32), _e.FMT_RISTRETTO)
+        return [out[i].tobytes() if st[i] == _e.LIZARD_OK else None for i in range(out.shape[0])]
+
+    @staticmethod
+    def map_to_curve_inverse(encodings, engine=None):
+        """[decompress(b_i).map_to_curve_inverse()] (lizard_ristretto.rs:232-238): per point a list of 16 `bytes | None` in the
+        reference's slot order for the decompressed representative (slots 0..7 even, 8..15 their negations); None in place of
+        the list for an invalid encoding (decompress() returned None)."""
+        _check_width(encodings, 32, "map_to_curve_inverse")
+        eng = engine or default_engine()
+        out, mask, ok = eng.ristretto_map_to_curve_inverse_batch(_cat(encodings, 32), _e.FMT_RISTRETTO)
+        return [[out[i, j].tobytes() if mask[i] >> j & 1 else None for j in range(16)] if ok[i] else None for i in range(out.shape[0])]
+
+    @staticmethod
+    def map_to_curve_restricted(inputs, engine=None):
+        """[RistrettoPoint::map_to_curve_restricted(b_i).compress()] (lizard_ristretto.rs:215-224): ValueError where the reference
+        panics, i.e. when the bottom bit of b[0] or one of the top two bits of b[31] is set"""
+        _check_width(inputs, 32, "map_to_curve_restricted")
+        for i, b in enumerate(inputs):
+            if b[0] & 0x01 or b[31] & 0xC0:
+                raise ValueError("map_to_curve_restricted: input %d has the bottom bit or one of the top two bits set" % i)
+        return RistrettoPoint.map_to_curve(inputs, engine=engine)
 
 
 def _check_width(items, width, what):

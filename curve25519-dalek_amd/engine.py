@@ -12,6 +12,7 @@ import numpy as np
 OK, NONE, SCALAR_FORMAT, VERIFY, ARRAY_LENGTH, PREHASHED_CONTEXT_LENGTH = 0, 1, 2, 3, 4, 5
 DOMAIN_SEPARATOR_LENGTH = 6      # hash-to-curve: a DST of 0 or more than 255 bytes
 H2C_NU, H2C_RO = 0, 1            # c25519_edwards_hash_to_curve_batch mode: encode_to_curve / hash_to_curve
+LIZARD_NONE, LIZARD_OK, LIZARD_BAD_ENCODING = 0, 1, 2      # per-item status of the Lizard decode
 FMT_EDWARDS_Y, FMT_RISTRETTO, FMT_RAW160 = 0, 1, 2
 POINT_DECODES, POINT_SMALL_ORDER, POINT_TORSION_FREE = 1, 2, 4      # flags of c25519_point_order_checks_batch
 Z_TRANSCRIPT, Z_DEVICE = 0, 1
@@ -148,6 +149,12 @@ def load_library():
         "c25519_ristretto_hash_from_bytes_batch": (i32, [vp, vp, vp, u64, C.c_int, vp]),
         "c25519_edwards_hash_to_curve_batch_dev": (i32, [vp, vp, vp, u64, u64, C.c_char_p, C.c_uint32, C.c_int, C.c_int, vp]),
         "c25519_edwards_hash_to_curve_batch": (i32, [vp, vp, vp, u64, C.c_char_p, C.c_uint32, C.c_int, C.c_int, vp]),
+        "c25519_ristretto_lizard_encode_sha256_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
+        "c25519_ristretto_lizard_encode_sha256_batch": (i32, [vp, vp, u64, C.c_int, vp]),
+        "c25519_ristretto_lizard_decode_sha256_batch_dev": (i32, [vp, vp, u64, C.c_int, vp, vp]),
+        "c25519_ristretto_lizard_decode_sha256_batch": (i32, [vp, vp, u64, C.c_int, vp, vp]),
+        "c25519_ristretto_map_to_curve_inverse_batch_dev": (i32, [vp, vp, u64, C.c_int, vp, vp, vp]),
+        "c25519_ristretto_map_to_curve_inverse_batch": (i32, [vp, vp, u64, C.c_int, vp, vp, vp]),
         "c25519_microbench": (C.c_double, [vp, C.c_int, C.c_int]),
         "c25519_selftest_field": (i32, [vp, C.c_int, C.c_int, vp, vp, u64, vp]),
         "c25519_selftest_scalar": (i32, [vp, C.c_int, vp, vp, u64, vp]),
@@ -181,6 +188,9 @@ ABI_SYMBOLS = [
     "c25519_ristretto_from_uniform_bytes_batch_dev", "c25519_ristretto_from_uniform_bytes_batch", "c25519_ristretto_map_to_curve_batch_dev",
     "c25519_ristretto_map_to_curve_batch", "c25519_ristretto_hash_from_bytes_batch_dev", "c25519_ristretto_hash_from_bytes_batch",
     "c25519_edwards_hash_to_curve_batch_dev", "c25519_edwards_hash_to_curve_batch",
+    "c25519_ristretto_lizard_encode_sha256_batch_dev", "c25519_ristretto_lizard_encode_sha256_batch",
+    "c25519_ristretto_lizard_decode_sha256_batch_dev", "c25519_ristretto_lizard_decode_sha256_batch",
+    "c25519_ristretto_map_to_curve_inverse_batch_dev", "c25519_ristretto_map_to_curve_inverse_batch",
 ]
 
 _PT = {FMT_EDWARDS_Y: 32, FMT_RISTRETTO: 32, FMT_RAW160: 160}
@@ -511,6 +521,35 @@ class Engine:
         st = self._chk(self.lib.c25519_edwards_hash_to_curve_batch_dev(self.ctx, msgs.data_ptr(), msg_off.data_ptr(), msgs.numel(), n, dst, len(dst), mode, out_fmt,
                                                                        out.data_ptr()), (OK, DOMAIN_SEPARATOR_LENGTH))
         return out if st == OK else st
+
+    # -- Lizard on device tensors (D = Sha256) --------------------------------------------------------------------------
+    def ristretto_lizard_encode_batch_t(self, data16, out_fmt=FMT_RISTRETTO):
+        """(n, 16) uint8 payloads -> (n, 32) CompressedRistretto or (n, 160) RAW160 uint8 tensor"""
+        n = self._t(data16, 16)
+        out = self._h2c_out_t(n, out_fmt)
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_lizard_encode_sha256_batch_dev(self.ctx, data16.data_ptr(), n, out_fmt, out.data_ptr()))
+        return out
+
+    def ristretto_lizard_decode_batch_t(self, points, in_fmt=FMT_RISTRETTO):
+        """-> (payloads (n, 16) uint8 tensor, zero unless OK; status (n,) uint8 tensor of LIZARD_*)"""
+        n = self._t(points, _PT[in_fmt]) if in_fmt in (FMT_RISTRETTO, FMT_RAW160) else points.shape[0]
+        out = self.torch.empty((n, 16), dtype=self.torch.uint8, device=self.device)
+        st = self.torch.empty((n,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_lizard_decode_sha256_batch_dev(self.ctx, points.data_ptr(), n, in_fmt, out.data_ptr(), st.data_ptr()))
+        return out, st
+
+    def ristretto_map_to_curve_inverse_batch_t(self, points, in_fmt=FMT_RISTRETTO):
+        """-> (preimages (n, 16, 32) uint8 tensor, an undefined slot zero; mask (n,) int16 tensor, bit j = slot j defined;
+        ok (n,) uint8 tensor, 1 = valid encoding (all ones for RAW160 input))"""
+        n = self._t(points, _PT[in_fmt]) if in_fmt in (FMT_RISTRETTO, FMT_RAW160) else points.shape[0]
+        out = self.torch.empty((n, 16, 32), dtype=self.torch.uint8, device=self.device)
+        mask = self.torch.empty((n,), dtype=self.torch.int16, device=self.device)
+        ok = self.torch.ones((n,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_map_to_curve_inverse_batch_dev(self.ctx, points.data_ptr(), n, in_fmt, out.data_ptr(), mask.data_ptr(), ok.data_ptr()))
+        return out, mask, ok
 
     # -- host-buffer API (numpy in / numpy out) ---------------------------------------------------
     @staticmethod
@@ -852,6 +891,35 @@ class Engine:
         st = self._chk(self.lib.c25519_edwards_hash_to_curve_batch(self.ctx, blob.ctypes.data, off.ctypes.data, n, dst, len(dst), mode, out_fmt, out.ctypes.data),
                        (OK, DOMAIN_SEPARATOR_LENGTH))
         return out if st == OK else st
+
+    # -- Lizard, host buffers (D = Sha256)
+    def ristretto_lizard_encode_batch(self, data16, out_fmt=FMT_RISTRETTO, out=None):
+        """(n, 16) payloads -> numpy (n, 32) CompressedRistretto or (n, 160) RAW160"""
+        a = _np8(data16, 16) if len(data16) else np.empty((0, 16), np.uint8); n = a.shape[0]
+        out = self._out(out, n, _PT.get(out_fmt, 32))
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_lizard_encode_sha256_batch(self.ctx, a.ctypes.data, n, out_fmt, out.ctypes.data))
+        return out
+
+    def ristretto_lizard_decode_batch(self, points, in_fmt=FMT_RISTRETTO, out=None, status=None):
+        """-> (payloads numpy (n, 16), zero unless OK; status numpy (n,) uint8 of LIZARD_*).  out / status: buffers to reuse"""
+        a = _np8(points, _PT.get(in_fmt, 32)) if len(points) else np.empty((0, _PT.get(in_fmt, 32)), np.uint8); n = a.shape[0]
+        out = self._out(out, n, 16)
+        st = self._out(status, n, 1)
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_lizard_decode_sha256_batch(self.ctx, a.ctypes.data, n, in_fmt, out.ctypes.data, st.ctypes.data))
+        return out, st
+
+    def ristretto_map_to_curve_inverse_batch(self, points, in_fmt=FMT_RISTRETTO, out=None):
+        """-> (preimages numpy (n, 16, 32), an undefined slot zero; mask numpy (n,) uint16, bit j = slot j defined;
+        ok numpy (n,) uint8, 1 = valid encoding (all ones for RAW160 input)).  out: an (n, 16, 32) uint8 buffer to reuse"""
+        a = _np8(points, _PT.get(in_fmt, 32)) if len(points) else np.empty((0, _PT.get(in_fmt, 32)), np.uint8); n = a.shape[0]
+        out = self._out(out, n, 512).reshape(n, 16, 32)
+        mask = np.empty((n,), np.uint16)
+        ok = np.ones((n,), np.uint8)
+        self._bind_stream()
+        self._chk(self.lib.c25519_ristretto_map_to_curve_inverse_batch(self.ctx, a.ctypes.data, n, in_fmt, out.ctypes.data, mask.ctypes.data, ok.ctypes.data))
+        return out, mask, ok
 
     def scalar_invert_batch(self, scalars):
         """-> (inverses (n,32), product of all inverses (32 bytes)); inputs must be canonical and non-zero."""

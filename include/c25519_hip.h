@@ -465,6 +465,27 @@ int32_t c25519_edwards_hash_to_curve_batch_dev(c25519_ctx *ctx, const uint8_t *d
 int32_t c25519_edwards_hash_to_curve_batch(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n,
                                            const uint8_t *dst, uint32_t dst_len, int mode, int out_fmt, uint8_t *out);
 
+/* ---- Lizard (curve25519-dalek's `lizard` feature, D = Sha256): an injective 16-byte -> Ristretto encoding and its inverse ------
+ * One item per lane, constant-time in the payload and the point (selects only).  in_fmt / out_fmt: C25519_FMT_RISTRETTO (n x 32)
+ * or C25519_FMT_RAW160 (n x 160; a RAW160 input is trusted to be a point, as in the MSM, and is used as given: the slot order of
+ * map_to_curve_inverse is that of this representative).  Any other format returns -(hipErrorInvalidValue); n == 0 returns C25519_OK. */
+#define C25519_LIZARD_NONE 0          /* no unique Lizard preimage (lizard_decode returned None) */
+#define C25519_LIZARD_OK 1
+#define C25519_LIZARD_BAD_ENCODING 2  /* in_fmt RISTRETTO only: not a canonical Ristretto encoding */
+/* RistrettoPoint::lizard_encode::<Sha256> (lizard/lizard_ristretto.rs:25-42): in n x 16 bytes, out n points. */
+int32_t c25519_ristretto_lizard_encode_sha256_batch_dev(c25519_ctx *ctx, const uint8_t *d_data16, uint64_t n, int out_fmt, uint8_t *d_out);
+int32_t c25519_ristretto_lizard_encode_sha256_batch(c25519_ctx *ctx, const uint8_t *data16, uint64_t n, int out_fmt, uint8_t *out);
+/* RistrettoPoint::lizard_decode::<Sha256> (lizard/lizard_ristretto.rs:46-75), after CompressedRistretto::decompress for in_fmt RISTRETTO:
+ * out16 n x 16 bytes (zero unless the status is C25519_LIZARD_OK), status n bytes C25519_LIZARD_*. */
+int32_t c25519_ristretto_lizard_decode_sha256_batch_dev(c25519_ctx *ctx, const uint8_t *d_in, uint64_t n, int in_fmt, uint8_t *d_out16, uint8_t *d_status);
+int32_t c25519_ristretto_lizard_decode_sha256_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int in_fmt, uint8_t *out16, uint8_t *status);
+/* RistrettoPoint::map_to_curve_inverse (lizard/lizard_ristretto.rs:232-238): out512 n x 16 x 32 bytes, slot j of item i at
+ * out512 + 512 i + 32 j (an undefined slot is all zero bytes); mask[i] bit j set when slot j is defined; ok[i] = 1 when the
+ * encoding is valid (in_fmt RISTRETTO only: for RAW160 ok is not written and may be NULL). */
+int32_t c25519_ristretto_map_to_curve_inverse_batch_dev(c25519_ctx *ctx, const uint8_t *d_in, uint64_t n, int in_fmt, uint8_t *d_out512, uint16_t *d_mask,
+                                                        uint8_t *d_ok);
+int32_t c25519_ristretto_map_to_curve_inverse_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int in_fmt, uint8_t *out512, uint16_t *mask, uint8_t *ok);
+
 /* ---- Scalar::invert_batch_alloc (scalar.rs:802-856): io[i] <- 1/io[i] mod l in place (HOST pointer; all inputs
  * must be canonical and non-zero, as in the reference); prod_inv (32 bytes, may be NULL) receives the product of
  * all inverses, the reference's return value. */

@@ -79,6 +79,21 @@ SQRT_AM2 = fsqrt((-486664) % P)
 if is_neg(SQRT_AM2):
     SQRT_AM2 = P - SQRT_AM2
 
+# Lizard (the reference's lizard/lizard_constants.rs, computed from the identities of its test_lizard_constants):
+# SQRT_ID = sqrt_ratio_i(i d, 1), the non-negative root; (d+1)/(d-1); -2/sqrt(a-d) and -2i/sqrt(a-d) from INVSQRT_A_MINUS_D;
+# -1/sqrt(1+d) from invsqrt, whose root is the non-negative one
+
+
+def ct_abs(x):
+    return P - x if is_neg(x) else x
+
+
+SQRT_ID = ct_abs(fsqrt(SQRT_M1 * D % P))
+DP1_OVER_DM1 = (D + 1) * inv((D - 1) % P) % P
+MDOUBLE_INVSQRT_A_MINUS_D = (-2 * INVSQRT_A_MINUS_D) % P
+MIDOUBLE_INVSQRT_A_MINUS_D = MDOUBLE_INVSQRT_A_MINUS_D * SQRT_M1 % P
+MINVSQRT_ONE_PLUS_D = (-ct_abs(inv(fsqrt((D + 1) % P)))) % P
+
 # scalar Montgomery constants (R = 2^260, 52-bit limbs)
 LFACTOR = (-pow(L, -1, 2**52)) % 2**52
 R = 2**260 % L
@@ -113,6 +128,13 @@ def sha512_constants():
     ps = _primes(80)
     K = [_iroot(p << (3 * 64), 3) & (2**64 - 1) for p in ps]     # frac(cbrt(p)) * 2^64
     H = [_iroot(p << (2 * 64), 2) & (2**64 - 1) for p in ps[:8]]  # frac(sqrt(p)) * 2^64
+    return K, H
+
+
+def sha256_constants():
+    ps = _primes(64)
+    K = [_iroot(p << (3 * 32), 3) & (2**32 - 1) for p in ps]     # frac(cbrt(p)) * 2^32
+    H = [_iroot(p << (2 * 32), 2) & (2**32 - 1) for p in ps[:8]]  # frac(sqrt(p)) * 2^32
     return K, H
 
 
@@ -219,6 +241,11 @@ def main():
         ("MONTGOMERY_A_NEG", (-MONT_A) % P, "-A (x1n of RFC 9380 G.2.1)"),
         ("H2C_C2", H2C_C2, "c2 = 2^((p+3)/8) of RFC 9380 G.2.1"),
         ("ED25519_SQRTAM2", SQRT_AM2, "sqrt(-486664), sgn0 = 0: the birational map to edwards25519 (RFC 9380 G.2.2)"),
+        ("LIZARD_SQRT_ID", SQRT_ID, "Lizard SQRT_ID = sqrt(i d), the non-negative root"),
+        ("LIZARD_DP1_OVER_DM1", DP1_OVER_DM1, "Lizard DP1_OVER_DM1 = (d+1)/(d-1)"),
+        ("LIZARD_MDOUBLE_INVSQRT_A_MINUS_D", MDOUBLE_INVSQRT_A_MINUS_D, "Lizard MDOUBLE_INVSQRT_A_MINUS_D = -2/sqrt(a-d)"),
+        ("LIZARD_MIDOUBLE_INVSQRT_A_MINUS_D", MIDOUBLE_INVSQRT_A_MINUS_D, "Lizard MIDOUBLE_INVSQRT_A_MINUS_D = -2i/sqrt(a-d)"),
+        ("LIZARD_MINVSQRT_ONE_PLUS_D", MINVSQRT_ONE_PLUS_D, "Lizard MINVSQRT_ONE_PLUS_D = -1/sqrt(1+d)"),
     ]
     for name, val, com in fe + fe_dev:
         dev.append(c_u32("C25519_" + name + "_26", limbs26(val), com))
@@ -226,6 +253,9 @@ def main():
     dev.append("#define C25519_L_W32 { %s }" % ", ".join("0x%08xu" % ((L >> (32 * i)) & 0xffffffff) for i in range(8)))
     dev.append("#define C25519_SHA512_K { %s }" % ", ".join("0x%016xULL" % v for v in K))
     dev.append("#define C25519_SHA512_IV { %s }" % ", ".join("0x%016xULL" % v for v in H))
+    K256, H256 = sha256_constants()
+    dev.append("#define C25519_SHA256_K { %s }" % ", ".join("0x%08xu" % v for v in K256))
+    dev.append("#define C25519_SHA256_IV { %s }" % ", ".join("0x%08xu" % v for v in H256))
     dev.append("#define C25519_KECCAK_RC { %s }" % ", ".join("0x%016xULL" % v for v in RC))
     dev.append("#define C25519_KECCAK_ROT { %s }" % ", ".join(str(rot[i % 5][i // 5]) for i in range(25)))
     dev.append("")
@@ -236,6 +266,8 @@ def main():
     # sanity: basepoint has order l, 2B / known facts
     assert (-BX * BX + BY * BY - 1 - D * BX * BX * BY * BY) % P == 0
     assert SQRT_AM2 * SQRT_AM2 % P == (-486664) % P and pow(H2C_C2, 4, P) == P - 4
+    assert SQRT_ID * SQRT_ID % P == SQRT_M1 * D % P and MINVSQRT_ONE_PLUS_D ** 2 * (1 + D) % P == 1
+    assert K256[0] == 0x428a2f98 and H256[0] == 0x6a09e667
     print("constants written")
 
 
