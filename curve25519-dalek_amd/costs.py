@@ -23,6 +23,8 @@ Formula sources (file:function):
   Ristretto decompression       257 S + 27 M                             ge26.h:ris_decompress
   Jacobi quartic points (4)     258 S + 40 M                             lizard.h:ris_to_jacobi_quartic
   e_inv_positive                257 S + 23 M                             lizard.h:jacobi_e_inv_positive (8 per decode / inverse)
+  Montgomery ladder step        5 M + 4 S + 0.1 M                        montgomery.h:mont_ladder_step (k_x25519, k_mont_mul, k_mont_mul_bits)
+  to_edwards                    255 S + 26 M + inversion / 16            montgomery.hip:k_mont_to_edwards_prep + k_ratio_p32 + k_mont_to_edwards
 """
 import math
 
@@ -170,6 +172,22 @@ def map_to_curve_inverse(compressed=True):
     return c
 
 
+def montgomery_mul_bits(nbits=255):
+    """montgomery.hip:k_mont_mul_bits (nbits = 255: k_mont_mul, the same count as x25519()): nbits ladder steps, then k_ratio_p32"""
+    c = _add({"M": nbits * 5.1, "S": nbits * 4}, {"M": 3, "S": 0}, _scaled(INV, 1.0 / CHUNK))
+    c["what"] = "%d x (5 M + 4 S + 10-product a24 mul) + 3 M + 1/16 inversion" % nbits
+    return c
+
+
+def montgomery_to_edwards():
+    """montgomery.hip: y = (u - 1) / (u + 1) by the batched division of finish.hip:k_ratio_p32 (4 M + 1/16 inversion), then
+    k_mont_to_edwards: the decompression (255 S + 22 M with T = X Y); the compression of the affine result is a canonical encoding, no
+    field operation.  (The per-lane arm pays a whole inversion, 254 S + 11 M, and 1 M instead of the batched division.)"""
+    c = _add({"M": 4, "S": 0}, _scaled(INV, 1.0 / CHUNK), {"M": 22, "S": 255})
+    c["what"] = "batched division (4 M + 1/16 inversion) + decompression (255 S + 22 M)"
+    return c
+
+
 def table():
     """Rows for DESIGN.md (python -m curve25519_dalek_amd.costs)."""
     rows = [("fixed base, radix 2^16 tables", fixed_base_wide(16)), ("fixed base, LDS comb", fixed_base_comb()),
@@ -177,7 +195,9 @@ def table():
             ("MSM 2^21 terms, raw points", msm(1 << 21, 17, 32768)), ("verify_batch 2^20, VerifyingKey", verify(1 << 20, 17, 32768)),
             ("verify_batch 2^20, keys as bytes", verify(1 << 20, 17, 32768, True)),
             ("Ristretto from_uniform_bytes", ristretto_from_uniform()), ("Edwards hash_to_curve (RO)", edwards_hash_to_curve()),
-            ("Lizard encode", lizard_encode()), ("Lizard decode (compressed in)", lizard_decode()), ("map_to_curve_inverse", map_to_curve_inverse())]
+            ("Lizard encode", lizard_encode()), ("Lizard decode (compressed in)", lizard_decode()), ("map_to_curve_inverse", map_to_curve_inverse()),
+            ("MontgomeryPoint mul / mul_bits_be 255", montgomery_mul_bits(255)), ("mul_bits_be 512", montgomery_mul_bits(512)),
+            ("MontgomeryPoint::to_edwards", montgomery_to_edwards())]
     return [(name, round(c["M"], 1), round(c["S"], 1), int(round(mac(c))), c["what"]) for name, c in rows]
 
 

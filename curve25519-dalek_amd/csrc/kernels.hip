@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "fe26x.h"
 #include "knobs.h"
+#include "montgomery.h"
 #ifndef C25519_PREPC_ATTR
 #define C25519_PREPC_ATTR
 #endif
@@ -615,32 +616,15 @@ __global__ void __launch_bounds__(256) C25519_X25519_ATTR k_x25519(const uint8_t
         if ((bit & 31) == 31 || i == 0) word = sk[(bit >> 5) * 256 + threadIdx.x] << (31 - (bit & 31));
         const u32 cur = word >> 31;
         word <<= 1;
-        const u32 sw = prev ^ cur;
-        fe_cswap(x0.U, x1.U, sw); fe_cswap(x0.W, x1.W, sw);
-        mont_diff_add_and_double(x0, x1, au);
+        mont_ladder_step(x0, x1, au, prev, cur);
         prev = cur;
     }
 #pragma unroll
     for (int w = 0; w < 8; w++) sk[w * 256 + threadIdx.x] = 0;        // the secret does not stay in LDS
-#else
-    // bit 254 -> position 255
-#pragma unroll
-    for (int i = 7; i > 0; i--) s[i] = (s[i] << 1) | (s[i - 1] >> 31);
-    s[0] <<= 1;
-    u32 prev = 0;
-#pragma unroll 1
-    for (int i = 0; i < 255; i++) {
-        u32 cur = s[7] >> 31;
-#pragma unroll
-        for (int k = 7; k > 0; k--) s[k] = (s[k] << 1) | (s[k - 1] >> 31);
-        s[0] <<= 1;
-        u32 sw = prev ^ cur;
-        fe_cswap(x0.U, x1.U, sw); fe_cswap(x0.W, x1.W, sw);
-        mont_diff_add_and_double(x0, x1, au);
-        prev = cur;
-    }
-#endif
     fe_cswap(x0.U, x1.U, prev); fe_cswap(x0.W, x1.W, prev);
+#else
+    mont_ladder_255(s, au, x0, x1);                             // montgomery.h: the ladder of Mul<&Scalar>, here on the clamped integer
+#endif
     p32_store(scratch, idx, x0.U, x0.U, x0.W);     // (U : W); the division is batched in k_ratio_p32
 }
 

@@ -22,6 +22,8 @@ error behaviour), batched, on top of Engine.  Reference entry points mirrored:
   EdwardsPoint::hash_to_curve / encode_to_curve::<Sha512>   curve25519-dalek/src/edwards.rs:710-750 (RFC 9380)
   RistrettoPoint::lizard_encode / lizard_decode::<Sha256>, map_to_curve_inverse, map_to_curve_restricted
                                               curve25519-dalek/src/lizard/lizard_ristretto.rs:25 / :46 / :232 / :215 (feature `lizard`)
+  MontgomeryPoint::mul (Mul<&Scalar>) / mul_bits_be / mul_base / to_edwards / mul_clamped / mul_base_clamped
+                                              curve25519-dalek/src/montgomery.rs:484 / :183 / :144 / :239 / :150 / :166
   EdwardsPoint::is_small_order / is_torsion_free   curve25519-dalek/src/edwards.rs:1405 / :1435;  VerifyingKey::is_weak  ed25519-dalek/src/verifying.rs:192
 
 Values cross this layer as the reference's wire types: Scalar = 32 canonical LE bytes,
@@ -256,6 +258,69 @@ class RistrettoPoint:
             if b[0] & 0x01 or b[31] & 0xC0:
                 raise ValueError("map_to_curve_restricted: input %d has the bottom bit or one of the top two bits set" % i)
         return RistrettoPoint.map_to_curve(inputs, engine=engine)
+
+
+class MontgomeryPoint:
+    """montgomery.rs, batched.  Points cross as MontgomeryPoint bytes (32-byte u-coordinates, decoded as FieldElement::from_bytes),
+    scalars as 32 bytes taken as given (the reference's Scalar holds a reduced value; the ladder skips bit 255 either way)."""
+
+    @staticmethod
+    def mul(points, scalars, engine=None):
+        """[&P_i * &s_i] (Mul<&Scalar>, montgomery.rs:484-492): the ladder over bits 254..0 of s_i, unclamped"""
+        _check_width(points, 32, "MontgomeryPoint.mul"); _check_width(scalars, 32, "MontgomeryPoint.mul")
+        if len(points) != len(scalars):
+            raise ValueError("MontgomeryPoint.mul: points and scalars must have equal length")
+        eng = engine or default_engine()
+        out = eng.montgomery_mul_batch(_cat(scalars, 32), _cat(points, 32))
+        return [out[i].tobytes() for i in range(out.shape[0])]
+
+    @staticmethod
+    def mul_bits_be(points, bits, engine=None):
+        """[P_i.mul_bits_be(bits_i)] (montgomery.rs:183-211): bits_i is a sequence of bools, most significant first, the same
+        length (at most 512) for every item"""
+        nbits = len(bits[0]) if len(bits) else 0
+        if any(len(b) != nbits for b in bits):
+            raise ValueError("MontgomeryPoint.mul_bits_be: every bit string must have the same length")
+        if nbits > _e.MONTGOMERY_MAX_BITS:
+            raise ValueError("MontgomeryPoint.mul_bits_be: at most %d bits" % _e.MONTGOMERY_MAX_BITS)
+        _check_width(points, 32, "MontgomeryPoint.mul_bits_be")
+        if len(points) != len(bits):
+            raise ValueError("MontgomeryPoint.mul_bits_be: points and bit strings must have equal length")
+        packed = np.packbits(np.asarray(bits, dtype=bool).reshape(len(bits), nbits), axis=1) if nbits else np.empty((len(bits), 0), np.uint8)
+        eng = engine or default_engine()
+        out = eng.montgomery_mul_bits_be_batch(packed, nbits, _cat(points, 32))
+        return [out[i].tobytes() for i in range(out.shape[0])]
+
+    @staticmethod
+    def mul_base(scalars, engine=None):
+        """[MontgomeryPoint::mul_base(&s_i)] = EdwardsPoint::mul_base(s_i).to_montgomery() (montgomery.rs:144-146), unclamped"""
+        _check_width(scalars, 32, "MontgomeryPoint.mul_base")
+        eng = engine or default_engine()
+        out = eng.montgomery_mul_base_batch(_cat(scalars, 32))
+        return [out[i].tobytes() for i in range(out.shape[0])]
+
+    @staticmethod
+    def mul_clamped(points, raw_bytes, engine=None):
+        """[P_i.mul_clamped(bytes_i)] (montgomery.rs:150-162): the X25519 ladder"""
+        if len(points) != len(raw_bytes):
+            raise ValueError("MontgomeryPoint.mul_clamped: points and scalars must have equal length")
+        return x25519(raw_bytes, points, engine=engine)
+
+    @staticmethod
+    def mul_base_clamped(raw_bytes, engine=None):
+        """[MontgomeryPoint::mul_base_clamped(bytes_i)] (montgomery.rs:166-174): the X25519 public-key path"""
+        return x25519_public_keys(raw_bytes, engine=engine)
+
+    @staticmethod
+    def to_edwards(points, signs, engine=None):
+        """[P_i.to_edwards(sign_i).map(|e| e.compress())] (montgomery.rs:239-268): 32 bytes, or None where the reference returns None
+        (u = -1, or u on the twist); sign_i is a u8, of which only bit 0 counts"""
+        _check_width(points, 32, "MontgomeryPoint.to_edwards")
+        if len(points) != len(signs):
+            raise ValueError("MontgomeryPoint.to_edwards: points and signs must have equal length")
+        eng = engine or default_engine()
+        out, st = eng.montgomery_to_edwards_batch(_cat(points, 32), np.asarray(signs, dtype=np.uint8), _e.FMT_EDWARDS_Y)
+        return [out[i].tobytes() if st[i] else None for i in range(out.shape[0])]
 
 
 def _check_width(items, width, what):

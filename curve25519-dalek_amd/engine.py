@@ -13,6 +13,7 @@ OK, NONE, SCALAR_FORMAT, VERIFY, ARRAY_LENGTH, PREHASHED_CONTEXT_LENGTH = 0, 1, 
 DOMAIN_SEPARATOR_LENGTH = 6      # hash-to-curve: a DST of 0 or more than 255 bytes
 H2C_NU, H2C_RO = 0, 1            # c25519_edwards_hash_to_curve_batch mode: encode_to_curve / hash_to_curve
 LIZARD_NONE, LIZARD_OK, LIZARD_BAD_ENCODING = 0, 1, 2      # per-item status of the Lizard decode
+MONTGOMERY_MAX_BITS = 512        # C25519_MONTGOMERY_MAX_BITS: the longest bit string of montgomery_mul_bits_be
 FMT_EDWARDS_Y, FMT_RISTRETTO, FMT_RAW160 = 0, 1, 2
 POINT_DECODES, POINT_SMALL_ORDER, POINT_TORSION_FREE = 1, 2, 4      # flags of c25519_point_order_checks_batch
 Z_TRANSCRIPT, Z_DEVICE = 0, 1
@@ -155,6 +156,14 @@ def load_library():
         "c25519_ristretto_lizard_decode_sha256_batch": (i32, [vp, vp, u64, C.c_int, vp, vp]),
         "c25519_ristretto_map_to_curve_inverse_batch_dev": (i32, [vp, vp, u64, C.c_int, vp, vp, vp]),
         "c25519_ristretto_map_to_curve_inverse_batch": (i32, [vp, vp, u64, C.c_int, vp, vp, vp]),
+        "c25519_montgomery_mul_batch_dev": (i32, [vp, vp, vp, u64, vp]),
+        "c25519_montgomery_mul_batch": (i32, [vp, vp, vp, u64, vp]),
+        "c25519_montgomery_mul_bits_be_batch_dev": (i32, [vp, vp, C.c_uint32, vp, u64, vp]),
+        "c25519_montgomery_mul_bits_be_batch": (i32, [vp, vp, C.c_uint32, vp, u64, vp]),
+        "c25519_montgomery_mul_base_batch_dev": (i32, [vp, vp, u64, vp]),
+        "c25519_montgomery_mul_base_batch": (i32, [vp, vp, u64, vp]),
+        "c25519_montgomery_to_edwards_batch_dev": (i32, [vp, vp, vp, u64, C.c_int, vp, vp]),
+        "c25519_montgomery_to_edwards_batch": (i32, [vp, vp, vp, u64, C.c_int, vp, vp]),
         "c25519_microbench": (C.c_double, [vp, C.c_int, C.c_int]),
         "c25519_selftest_field": (i32, [vp, C.c_int, C.c_int, vp, vp, u64, vp]),
         "c25519_selftest_scalar": (i32, [vp, C.c_int, vp, vp, u64, vp]),
@@ -191,6 +200,8 @@ ABI_SYMBOLS = [
     "c25519_ristretto_lizard_encode_sha256_batch_dev", "c25519_ristretto_lizard_encode_sha256_batch",
     "c25519_ristretto_lizard_decode_sha256_batch_dev", "c25519_ristretto_lizard_decode_sha256_batch",
     "c25519_ristretto_map_to_curve_inverse_batch_dev", "c25519_ristretto_map_to_curve_inverse_batch",
+    "c25519_montgomery_mul_batch_dev", "c25519_montgomery_mul_batch", "c25519_montgomery_mul_bits_be_batch_dev", "c25519_montgomery_mul_bits_be_batch",
+    "c25519_montgomery_mul_base_batch_dev", "c25519_montgomery_mul_base_batch", "c25519_montgomery_to_edwards_batch_dev", "c25519_montgomery_to_edwards_batch",
 ]
 
 _PT = {FMT_EDWARDS_Y: 32, FMT_RISTRETTO: 32, FMT_RAW160: 160}
@@ -550,6 +561,49 @@ class Engine:
         self._bind_stream()
         self._chk(self.lib.c25519_ristretto_map_to_curve_inverse_batch_dev(self.ctx, points.data_ptr(), n, in_fmt, out.data_ptr(), mask.data_ptr(), ok.data_ptr()))
         return out, mask, ok
+
+    # -- MontgomeryPoint on device tensors (montgomery.rs) ------------------------------------------------------------
+    def montgomery_mul_batch_t(self, k, u, out=None):
+        """u(k_i * P_i), the unclamped ladder over bits 254..0 of k_i (Mul<&Scalar>, montgomery.rs:484-492): (n, 32) uint8 tensors"""
+        n = self._t(k, 32)
+        assert self._t(u, 32) == n
+        if out is None:
+            out = self.torch.empty((n, 32), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        self._chk(self.lib.c25519_montgomery_mul_batch_dev(self.ctx, k.data_ptr(), u.data_ptr(), n, out.data_ptr()))
+        return out
+
+    def montgomery_mul_bits_be_batch_t(self, bits, nbits, u, out=None):
+        """mul_bits_be (montgomery.rs:183-211): bits (n, ceil(nbits/8)) uint8 tensor, MSB first; u (n, 32) -> (n, 32)"""
+        n = self._t(u, 32)
+        nb = (nbits + 7) // 8
+        if nb:
+            assert bits.is_cuda and bits.dtype == self.torch.uint8 and bits.is_contiguous() and bits.numel() == n * nb
+        if out is None:
+            out = self.torch.empty((n, 32), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        self._chk(self.lib.c25519_montgomery_mul_bits_be_batch_dev(self.ctx, bits.data_ptr() if nb else None, nbits, u.data_ptr(), n, out.data_ptr()))
+        return out
+
+    def montgomery_mul_base_batch_t(self, scalars, out=None):
+        """MontgomeryPoint::mul_base (montgomery.rs:144-146), unclamped: (n, 32) -> (n, 32)"""
+        n = self._t(scalars, 32)
+        if out is None:
+            out = self.torch.empty((n, 32), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        self._chk(self.lib.c25519_montgomery_mul_base_batch_dev(self.ctx, scalars.data_ptr(), n, out.data_ptr()))
+        return out
+
+    def montgomery_to_edwards_batch_t(self, u, signs, out_fmt=FMT_EDWARDS_Y):
+        """to_edwards(sign) (montgomery.rs:239-268): u (n, 32), signs (n,) uint8 -> (points (n, 32) or (n, 160), zero where None;
+        status (n,) uint8, 1 = Some)"""
+        n = self._t(u, 32)
+        assert signs.is_cuda and signs.dtype == self.torch.uint8 and signs.is_contiguous() and signs.numel() == n
+        out = self.torch.empty((n, _PT.get(out_fmt, 32)), dtype=self.torch.uint8, device=self.device)
+        st = self.torch.empty((n,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        self._chk(self.lib.c25519_montgomery_to_edwards_batch_dev(self.ctx, u.data_ptr(), signs.data_ptr(), n, out_fmt, out.data_ptr(), st.data_ptr()))
+        return out, st
 
     # -- host-buffer API (numpy in / numpy out) ---------------------------------------------------
     @staticmethod
@@ -920,6 +974,46 @@ class Engine:
         self._bind_stream()
         self._chk(self.lib.c25519_ristretto_map_to_curve_inverse_batch(self.ctx, a.ctypes.data, n, in_fmt, out.ctypes.data, mask.ctypes.data, ok.ctypes.data))
         return out, mask, ok
+
+    # -- MontgomeryPoint, host buffers
+    def montgomery_mul_batch(self, k, u, out=None):
+        """u(k_i * P_i), unclamped (Mul<&Scalar>, montgomery.rs:484-492) -> numpy (n, 32)"""
+        k = _np8(k, 32); u = _np8(u, 32); n = k.shape[0]
+        assert u.shape[0] == n
+        out = self._out(out, n, 32)
+        self._bind_stream()
+        self._chk(self.lib.c25519_montgomery_mul_batch(self.ctx, k.ctypes.data, u.ctypes.data, n, out.ctypes.data))
+        return out
+
+    def montgomery_mul_bits_be_batch(self, bits, nbits, u, out=None):
+        """mul_bits_be (montgomery.rs:183-211): bits (n, ceil(nbits/8)) MSB first, one nbits for all items -> numpy (n, 32)"""
+        u = _np8(u, 32); n = u.shape[0]
+        nb = (nbits + 7) // 8
+        b = _np8(bits, nb) if nb else np.empty((n, 0), np.uint8)
+        assert b.shape[0] == n
+        out = self._out(out, n, 32)
+        self._bind_stream()
+        self._chk(self.lib.c25519_montgomery_mul_bits_be_batch(self.ctx, b.ctypes.data if nb else None, nbits, u.ctypes.data, n, out.ctypes.data))
+        return out
+
+    def montgomery_mul_base_batch(self, scalars, out=None):
+        """MontgomeryPoint::mul_base (montgomery.rs:144-146), unclamped -> numpy (n, 32)"""
+        s = _np8(scalars, 32); n = s.shape[0]
+        out = self._out(out, n, 32)
+        self._bind_stream()
+        self._chk(self.lib.c25519_montgomery_mul_base_batch(self.ctx, s.ctypes.data, n, out.ctypes.data))
+        return out
+
+    def montgomery_to_edwards_batch(self, u, signs, out_fmt=FMT_EDWARDS_Y, out=None):
+        """to_edwards(sign) (montgomery.rs:239-268) -> (points numpy (n, 32) or (n, 160), zero where None; status numpy (n,) uint8, 1 = Some)"""
+        u = _np8(u, 32); n = u.shape[0]
+        sg = np.ascontiguousarray(np.asarray(signs, dtype=np.uint8).reshape(-1))
+        assert sg.shape[0] == n
+        out = self._out(out, n, _PT.get(out_fmt, 32))
+        st = np.empty((n,), np.uint8)
+        self._bind_stream()
+        self._chk(self.lib.c25519_montgomery_to_edwards_batch(self.ctx, u.ctypes.data, sg.ctypes.data, n, out_fmt, out.ctypes.data, st.ctypes.data))
+        return out, st
 
     def scalar_invert_batch(self, scalars):
         """-> (inverses (n,32), product of all inverses (32 bytes)); inputs must be canonical and non-zero."""

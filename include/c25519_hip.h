@@ -486,6 +486,32 @@ int32_t c25519_ristretto_map_to_curve_inverse_batch_dev(c25519_ctx *ctx, const u
                                                         uint8_t *d_ok);
 int32_t c25519_ristretto_map_to_curve_inverse_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int in_fmt, uint8_t *out512, uint16_t *mask, uint8_t *ok);
 
+/* ---- MontgomeryPoint (montgomery.rs): the unclamped ladder, the fixed base and the map back to Edwards form ----------------------
+ * One item per lane, constant-time in the scalar, the bits and the point (selects only).  u: n x 32 MontgomeryPoint bytes, decoded as
+ * FieldElement::from_bytes (bit 255 ignored, values >= p accepted); out: n x 32 MontgomeryPoint bytes, the canonical u of the result,
+ * all zero where the ladder ends at W = 0 (as_affine, montgomery.rs:409).  n == 0 returns C25519_OK. */
+#define C25519_MONTGOMERY_MAX_BITS 512u
+/* impl Mul<&Scalar> for &MontgomeryPoint (montgomery.rs:484-492): out[i] = u(k[i] * P_i) over bits 254..0 of k[i] as given -- no
+ * clamping, no reduction; bit 255 is skipped, as bits_le().rev().skip(1) skips it.  k: n x 32. */
+int32_t c25519_montgomery_mul_batch_dev(c25519_ctx *ctx, const uint8_t *d_k, const uint8_t *d_u, uint64_t n, uint8_t *d_out);
+int32_t c25519_montgomery_mul_batch(c25519_ctx *ctx, const uint8_t *k, const uint8_t *u, uint64_t n, uint8_t *out);
+/* MontgomeryPoint::mul_bits_be (montgomery.rs:183-211): the same ladder over nbits big-endian bits per item, packed MSB first into
+ * ceil(nbits / 8) bytes (bits: n x ceil(nbits / 8); the padding bits of the last byte are ignored).  nbits is one value for the call,
+ * 0 <= nbits <= C25519_MONTGOMERY_MAX_BITS, else -(hipErrorInvalidValue); nbits == 0 gives u = 0.  The running time depends on nbits only. */
+int32_t c25519_montgomery_mul_bits_be_batch_dev(c25519_ctx *ctx, const uint8_t *d_bits, uint32_t nbits, const uint8_t *d_u, uint64_t n, uint8_t *d_out);
+int32_t c25519_montgomery_mul_bits_be_batch(c25519_ctx *ctx, const uint8_t *bits, uint32_t nbits, const uint8_t *u, uint64_t n, uint8_t *out);
+/* MontgomeryPoint::mul_base (montgomery.rs:144-146) = EdwardsPoint::mul_base(s).to_montgomery(), unclamped: the fixed-base kernels of
+ * c25519_mul_base_batch (constant-time tables unless C25519_FLAG_VARTIME_TABLES) and the to_montgomery map.  scalars: n x 32. */
+int32_t c25519_montgomery_mul_base_batch_dev(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, uint8_t *d_out);
+int32_t c25519_montgomery_mul_base_batch(c25519_ctx *ctx, const uint8_t *scalars, uint64_t n, uint8_t *out);
+/* MontgomeryPoint::to_edwards (montgomery.rs:239-268): y = (u - 1) / (u + 1), y_bytes[31] ^= signs[i] << 7 (in 8 bits: only bit 0 of
+ * the sign counts), then CompressedEdwardsY::decompress.  signs: n bytes.  out_fmt C25519_FMT_EDWARDS_Y (n x 32, the compression of the
+ * decompressed point: for u = 0 with sign 1 that is y without the sign bit) or C25519_FMT_RAW160 (n x 160); any other format returns
+ * -(hipErrorInvalidValue).  status[i] = 1 for Some, 0 for None (u = -1, or u on the twist); a None item's output is all zero. */
+int32_t c25519_montgomery_to_edwards_batch_dev(c25519_ctx *ctx, const uint8_t *d_u, const uint8_t *d_signs, uint64_t n, int out_fmt, uint8_t *d_out,
+                                               uint8_t *d_status);
+int32_t c25519_montgomery_to_edwards_batch(c25519_ctx *ctx, const uint8_t *u, const uint8_t *signs, uint64_t n, int out_fmt, uint8_t *out, uint8_t *status);
+
 /* ---- Scalar::invert_batch_alloc (scalar.rs:802-856): io[i] <- 1/io[i] mod l in place (HOST pointer; all inputs
  * must be canonical and non-zero, as in the reference); prod_inv (32 bytes, may be NULL) receives the product of
  * all inverses, the reference's return value. */
