@@ -15,10 +15,9 @@
 #include "sc_sha.h"
 #include "msm_internal.h"
 #include "ffi.h"
+#include "capi_util.h"
 
 using namespace c25519;
-
-#define EXPORT extern "C" __attribute__((visibility("default")))
 
 // ------------------------------------------------------------------------------------------------
 int32_t c25519_fail(c25519_ctx *ctx, hipError_t e, const char *where) {
@@ -27,11 +26,6 @@ int32_t c25519_fail(c25519_ctx *ctx, hipError_t e, const char *where) {
     ctx->err = buf;
     return -(int32_t)e;
 }
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
 
 int32_t ctx_reserve(c25519_ctx *ctx, devbuf &b, size_t bytes) {
     if (b.cap >= bytes) return 0;
@@ -388,6 +382,23 @@ int32_t ffi_end(c25519_ctx *ctx, uint64_t h2d_bytes, uint64_t d2h_bytes) {
     if (e2 != hipSuccess) return c25519_fail(ctx, e2, "hipStreamSynchronize(h2d)");
     return C25519_OK;
 }
+int32_t ffi_upload_msgs(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, const char *what, size_t c_bytes, ffi_msgs &m,
+                        stream_wipe *wipe, size_t c_secret) {
+    for (uint64_t i = 0; i < n; i++) if (msg_off[i] > msg_off[i + 1]) return bad_arg(ctx, what);
+    const uint64_t mlen = msg_off[n];
+    int32_t r;
+    if ((r = ctx_reserve(ctx, ctx->tmp_a, mlen + 64)) || (r = ctx_reserve(ctx, ctx->tmp_b, (n + 1) * 8)) || (r = ctx_reserve(ctx, ctx->tmp_c, c_bytes))) return r;
+    uint8_t *dmsg = (uint8_t *)ctx->tmp_a.p;
+    uint64_t *doff = (uint64_t *)ctx->tmp_b.p;
+    if (wipe) wipe->add(ctx->tmp_c.p, c_secret);
+    if ((r = ffi_begin(ctx))) return r;
+    ffi_guard guard(ctx);                                 // an early exit below still drains the copy stream (before the caller's wipe)
+    if (mlen) HIPCHK(hipMemcpyAsync(dmsg, msgs, mlen, hipMemcpyHostToDevice, ctx->s_h2d));
+    HIPCHK(hipMemcpyAsync(doff, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_h2d));
+    guard.dismiss();                                      // ffi_pipeline calls ffi_end on every path
+    m = {dmsg, doff, mlen, mlen + (n + 1) * 8};
+    return C25519_OK;
+}
 // SMALL host-pointer calls (a few hundred KB at most): the pieces of the input are staged into ONE page-locked buffer and go up with ONE asynchronous
 // copy on the COMPUTE stream -- no copy stream, no events, no second synchronisation.  The chunked path above costs such a call a dozen runtime
 // calls and two pageable copies (each staged by the runtime on its own): ~45 us of a 185 us MSM of 256 terms.  d[i]: where piece i landed
@@ -399,7 +410,7 @@ int32_t ffi_small_upload(c25519_ctx *ctx, int pieces, const void *const *src, co
     HIPCHK(hipSetDevice(ctx->device));
     ctx->ffi_t0 = wall_ms();
     size_t off[8], total = 0;
-    if (pieces > 8) { ctx->err = "ffi_small_upload: too many pieces"; return -(int32_t)hipErrorInvalidValue; }
+    if (pieces > 8) return bad_arg(ctx, "ffi_small_upload: too many pieces");
     for (int i = 0; i < pieces; i++) { off[i] = total; total += (bytes[i] + 255) & ~(size_t)255; }
     int32_t r;
     // min_stage: what the rest of the call will ask of the staging buffer (the strict z-mode of verify_batch keeps its host copies there): it must not
@@ -453,7 +464,7 @@ EXPORT const char *c25519_last_kernel_name(const c25519_ctx *ctx, int which) { r
 // ---- fixed base --------------------------------------------------------------------------------
 int32_t mul_base_impl(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, int out_fmt, uint8_t *d_out, bool secret, const uint32_t *table_ct) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (out_fmt != C25519_FMT_EDWARDS_Y && out_fmt != C25519_FMT_RISTRETTO && out_fmt != C25519_FMT_RAW160) { ctx->err = "mul_base: out_fmt must be 0, 1 or 2"; return -(int32_t)hipErrorInvalidValue; }
+    if (out_fmt != C25519_FMT_EDWARDS_Y && out_fmt != C25519_FMT_RISTRETTO && out_fmt != C25519_FMT_RAW160) return bad_arg(ctx, "mul_base: out_fmt must be 0, 1 or 2");
     if (out_fmt == C25519_FMT_EDWARDS_Y) {
         int32_t r;
         if ((r = ctx_reserve(ctx, ctx->scratch, n * 128)) || (r = ctx_reserve(ctx, ctx->prefix, n * 48))) return r;
@@ -495,22 +506,14 @@ EXPORT int32_t c25519_mul_base_batch_vartime_dev(c25519_ctx *ctx, const uint8_t 
     return mul_base_impl(ctx, d_scalars, n, out_fmt, d_out, false, nullptr);
 }
 
-static inline int32_t reserve2(c25519_ctx *ctx, devbuf &a, size_t na, devbuf &b, size_t nb) { int32_t r = ctx_reserve(ctx, a, na ? na : 16); return r ? r : ctx_reserve(ctx, b, nb ? nb : 16); }
 static int32_t mul_base_host(c25519_ctx *ctx, const uint8_t *scalars, uint64_t n, int out_fmt, uint8_t *out, bool secret, bool clamp, const uint32_t *table_ct) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (out_fmt < 0 || out_fmt > 2) { ctx->err = "mul_base: out_fmt must be 0, 1 or 2"; return -(int32_t)hipErrorInvalidValue; }
-    const size_t osz = out_fmt == C25519_FMT_RAW160 ? 160 : 32;
-    int32_t r;
-    if ((r = reserve2(ctx, ctx->tmp_a, n * 32, ctx->tmp_b, n * osz))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    stream_wipe wipe(ctx->stream);
-    if (secret) wipe.add(d_in, n * 32);                   // the staged scalars
-    const ffi_in in = {scalars, d_in, 32};
-    const ffi_out o = {out, d_out, osz};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 18), &in, 1, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t {
-        if (clamp) HIPCHK(launch_clamp(d_in + lo * 32, m, d_in + lo * 32, ctx->stream));
-        return mul_base_impl(ctx, d_in + lo * 32, m, out_fmt, d_out + lo * osz, secret, table_ct);
-    });
+    if (out_fmt < 0 || out_fmt > 2) return bad_arg(ctx, "mul_base: out_fmt must be 0, 1 or 2");
+    return ffi_twin(ctx, n, 1u << 18, {{scalars, 32, FFI_TMP_A, 0, secret}}, {{out, point_bytes(out_fmt), FFI_TMP_B}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) -> int32_t {
+                        if (clamp) HIPCHK(launch_clamp(d_in[0], m, d_in[0], ctx->stream));
+                        return mul_base_impl(ctx, d_in[0], m, out_fmt, d_out[0], secret, table_ct);
+                    });
 }
 EXPORT int32_t c25519_mul_base_batch(c25519_ctx *ctx, const uint8_t *scalars, uint64_t n, int out_fmt, uint8_t *out) {
     return mul_base_host(ctx, scalars, n, out_fmt, out, ctx_secret_default(ctx), false, nullptr);
@@ -565,11 +568,11 @@ EXPORT void c25519_basetable_destroy(c25519_ctx *ctx, c25519_basetable *t) {
     delete t;
 }
 EXPORT int32_t c25519_mul_table_batch_dev(c25519_ctx *ctx, const c25519_basetable *t, const uint8_t *d_scalars, uint64_t n, int out_fmt, uint8_t *d_out) {
-    if (!t) { ctx->err = "mul_table: null table"; return -(int32_t)hipErrorInvalidValue; }
+    if (!t) return bad_arg(ctx, "mul_table: null table");
     return mul_base_impl(ctx, d_scalars, n, out_fmt, d_out, true, t->d_table);
 }
 EXPORT int32_t c25519_mul_table_batch(c25519_ctx *ctx, const c25519_basetable *t, const uint8_t *scalars, uint64_t n, int out_fmt, uint8_t *out) {
-    if (!t) { ctx->err = "mul_table: null table"; return -(int32_t)hipErrorInvalidValue; }
+    if (!t) return bad_arg(ctx, "mul_table: null table");
     return mul_base_host(ctx, scalars, n, out_fmt, out, true, false, t->d_table);
 }
 
@@ -595,15 +598,8 @@ EXPORT int32_t c25519_x25519_base_batch_dev(c25519_ctx *ctx, const uint8_t *d_k,
 }
 EXPORT int32_t c25519_x25519_base_batch(c25519_ctx *ctx, const uint8_t *k, uint64_t n, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    int32_t r;
-    if ((r = reserve2(ctx, ctx->tmp_a, n * 32, ctx->tmp_b, n * 32))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    stream_wipe wipe(ctx->stream);
-    wipe.add(d_in, n * 32);                               // the staged secrets
-    const ffi_in in = {k, d_in, 32};
-    const ffi_out o = {out, d_out, 32};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 18), &in, 1, &o, 1,
-                        [&](uint64_t lo, uint64_t m) -> int32_t { return c25519_x25519_base_batch_dev(ctx, d_in + lo * 32, m, d_out + lo * 32); });
+    return ffi_twin(ctx, n, 1u << 18, {{k, 32, FFI_TMP_A, 0, true}}, {{out, 32, FFI_TMP_B}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_x25519_base_batch_dev(ctx, d_in[0], m, d_out[0]); });
 }
 // the ladder + the batched division for n units on stream st; scratch / prefix: n x 128 / n x 48 bytes of the caller's
 static int32_t x25519_enqueue(c25519_ctx *ctx, hipStream_t st, const uint8_t *d_k, const uint8_t *d_u, uint64_t n, uint32_t *scratch, uint32_t *prefix, uint8_t *d_out, hipEvent_t *ring) {
@@ -682,7 +678,7 @@ static int32_t decompress_enqueue(c25519_ctx *ctx, const uint8_t *d_in, uint64_t
 }
 EXPORT int32_t c25519_decompress_batch_dev(c25519_ctx *ctx, const uint8_t *d_in, uint64_t n, int in_fmt, uint8_t *d_out, uint8_t *d_ok) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (in_fmt != C25519_FMT_EDWARDS_Y && in_fmt != C25519_FMT_RISTRETTO) { ctx->err = "decompress: in_fmt must be 0 or 1"; return -(int32_t)hipErrorInvalidValue; }
+    if (in_fmt != C25519_FMT_EDWARDS_Y && in_fmt != C25519_FMT_RISTRETTO) return bad_arg(ctx, "decompress: in_fmt must be 0 or 1");
     HIPCHK(hipMemsetAsync(ctx->d_flag, 0, 4, ctx->stream));
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     int32_t r = decompress_enqueue(ctx, d_in, n, in_fmt, d_out, d_ok);
@@ -695,15 +691,10 @@ EXPORT int32_t c25519_decompress_batch_dev(c25519_ctx *ctx, const uint8_t *d_in,
 }
 EXPORT int32_t c25519_decompress_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int in_fmt, uint8_t *out, uint8_t *ok) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (in_fmt != C25519_FMT_EDWARDS_Y && in_fmt != C25519_FMT_RISTRETTO) { ctx->err = "decompress: in_fmt must be 0 or 1"; return -(int32_t)hipErrorInvalidValue; }
-    int32_t r;
-    if ((r = reserve2(ctx, ctx->tmp_a, n * 32, ctx->tmp_b, n * 160)) || (r = ctx_reserve(ctx, ctx->tmp_c, n + 16))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p, *d_ok = (uint8_t *)ctx->tmp_c.p;
+    if (in_fmt != C25519_FMT_EDWARDS_Y && in_fmt != C25519_FMT_RISTRETTO) return bad_arg(ctx, "decompress: in_fmt must be 0 or 1");
     HIPCHK(hipMemsetAsync(ctx->d_flag, 0, 4, ctx->stream));
-    const ffi_in i1 = {in, d_in, 32};
-    const ffi_out o[2] = {{out, d_out, 160}, {ok, d_ok, 1}};
-    r = ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 17), &i1, 1, o, 2,
-                     [&](uint64_t lo, uint64_t m) -> int32_t { return decompress_enqueue(ctx, d_in + lo * 32, m, in_fmt, d_out + lo * 160, d_ok + lo); });
+    const int32_t r = ffi_twin(ctx, n, 1u << 17, {{in, 32, FFI_TMP_A}}, {{out, 160, FFI_TMP_B}, {ok, 1, FFI_TMP_C, 16}},
+                               [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return decompress_enqueue(ctx, d_in[0], m, in_fmt, d_out[0], d_out[1]); });
     if (r) return r;
     uint32_t *bad = (uint32_t *)ctx->h_msm;
     HIPCHK(hipMemcpyAsync(bad, ctx->d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -712,7 +703,7 @@ EXPORT int32_t c25519_decompress_batch(c25519_ctx *ctx, const uint8_t *in, uint6
 }
 EXPORT int32_t c25519_compress_batch_dev(c25519_ctx *ctx, const uint8_t *d_in, uint64_t n, int out_fmt, uint8_t *d_out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (out_fmt != C25519_FMT_EDWARDS_Y && out_fmt != C25519_FMT_RISTRETTO) { ctx->err = "compress: out_fmt must be 0 or 1"; return -(int32_t)hipErrorInvalidValue; }
+    if (out_fmt != C25519_FMT_EDWARDS_Y && out_fmt != C25519_FMT_RISTRETTO) return bad_arg(ctx, "compress: out_fmt must be 0 or 1");
     if (out_fmt == C25519_FMT_RISTRETTO) {
         HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
         HIPCHK(launch_compress_ristretto(d_in, n, d_out, ctx->stream));
@@ -733,13 +724,8 @@ EXPORT int32_t c25519_compress_batch_dev(c25519_ctx *ctx, const uint8_t *d_in, u
 }
 EXPORT int32_t c25519_compress_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int out_fmt, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    int32_t r;
-    if ((r = reserve2(ctx, ctx->tmp_a, n * 160, ctx->tmp_b, n * 32))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    const ffi_in i1 = {in, d_in, 160};
-    const ffi_out o = {out, d_out, 32};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 17), &i1, 1, &o, 1,
-                        [&](uint64_t lo, uint64_t m) -> int32_t { return c25519_compress_batch_dev(ctx, d_in + lo * 160, m, out_fmt, d_out + lo * 32); });
+    return ffi_twin(ctx, n, 1u << 17, {{in, 160, FFI_TMP_A}}, {{out, 32, FFI_TMP_B}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_compress_batch_dev(ctx, d_in[0], m, out_fmt, d_out[0]); });
 }
 
 // ---- EdwardsPoint::to_montgomery_batch (edwards.rs:595-612) -------------------------------------------------
@@ -755,12 +741,7 @@ EXPORT int32_t c25519_to_montgomery_batch_dev(c25519_ctx *ctx, const uint8_t *d_
 }
 EXPORT int32_t c25519_to_montgomery_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    int32_t r;
-    if ((r = reserve2(ctx, ctx->tmp_a, n * 160, ctx->tmp_b, n * 32))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    const ffi_in i1 = {in, d_in, 160};
-    const ffi_out o = {out, d_out, 32};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 17), &i1, 1, &o, 1,
-                        [&](uint64_t lo, uint64_t m) -> int32_t { return c25519_to_montgomery_batch_dev(ctx, d_in + lo * 160, m, d_out + lo * 32); });
+    return ffi_twin(ctx, n, 1u << 17, {{in, 160, FFI_TMP_A}}, {{out, 32, FFI_TMP_B}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_to_montgomery_batch_dev(ctx, d_in[0], m, d_out[0]); });
 }
 

@@ -15,16 +15,9 @@
 #include "sc28.h"
 #include "fe9_probe.h"
 #include "ctx.h"
-
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
+#include "capi_util.h"
 
 namespace c25519 {
-static inline unsigned div_up(u64 a, u64 b) { return (unsigned)((a + b - 1) / b); }
 
 // ================================================================================================
 // device self-test of the scalar arithmetic (sc28.h; reference: u64/scalar.rs:66-320, scalar.rs:248-263)

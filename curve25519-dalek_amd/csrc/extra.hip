@@ -22,17 +22,10 @@
 #include "ctx.h"
 #include "msm_internal.h"
 #include "ffi.h"
+#include "capi_util.h"
 #include <stdexcept>
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
-
-static inline unsigned dup64(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
 
 struct c25519_precomp { uint32_t *d_table; uint64_t n; c25519::msm_merged m; };
 
@@ -168,7 +161,7 @@ __global__ void __launch_bounds__(256) k_scalar_invert(uint8_t *__restrict__ io,
 EXPORT c25519_precomp *c25519_precomp_create(c25519_ctx *ctx, const uint8_t *static_points, uint64_t n, int in_fmt) {
     if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
     if (in_fmt < 0 || in_fmt > 2) { ctx->err = "precomp_create: bad in_fmt"; return nullptr; }
-    size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32;
+    size_t psz = point_bytes(in_fmt);
     c25519_precomp *p = new c25519_precomp{nullptr, n, {}};
     msm_merged_layout(n, p->m);
     if (hipMalloc((void **)&p->d_table, (size_t)(n ? n : 1) * p->m.K * PTS_BYTES) != hipSuccess) { ctx->err = "precomp_create: hipMalloc failed"; delete p; return nullptr; }
@@ -195,11 +188,11 @@ EXPORT uint64_t c25519_precomp_len(const c25519_precomp *p) { return p ? p->n : 
 EXPORT int32_t c25519_precomp_msm_vartime(c25519_ctx *ctx, const c25519_precomp *p, const uint8_t *static_scalars, uint64_t n_static_scalars,
                                           const uint8_t *dyn_scalars, const uint8_t *dyn_points, uint64_t n_dyn, int in_fmt, int out_fmt, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (out_fmt < 0 || out_fmt > 2) { ctx->err = "precomp_msm: bad out_fmt"; return -(int32_t)hipErrorInvalidValue; }
-    if (n_static_scalars > p->n) { ctx->err = "precomp_msm: more static scalars than static points (precomputed_straus.rs:86)"; return -(int32_t)hipErrorInvalidValue; }
+    if (out_fmt < 0 || out_fmt > 2) return bad_arg(ctx, "precomp_msm: bad out_fmt");
+    if (n_static_scalars > p->n) return bad_arg(ctx, "precomp_msm: more static scalars than static points (precomputed_straus.rs:86)");
     const uint64_t ns = n_static_scalars;
     ge_p3 R = ge_identity();
-    size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32;
+    size_t psz = point_bytes(in_fmt);
     int32_t r;
     hipStream_t st = ctx->stream;
     HIPCHK(hipEventRecord(ctx->ev0, st));
@@ -230,10 +223,10 @@ EXPORT int32_t c25519_precomp_msm_vartime(c25519_ctx *ctx, const c25519_precomp 
 // ---- regular-schedule multiscalar multiplication -------------------------------------------------------------------
 EXPORT int32_t c25519_msm_consttime(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, int out_fmt, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (out_fmt < 0 || out_fmt > 2) { ctx->err = "msm_consttime: bad out_fmt"; return -(int32_t)hipErrorInvalidValue; }
+    if (out_fmt < 0 || out_fmt > 2) return bad_arg(ctx, "msm_consttime: bad out_fmt");
     ge_p3 R = ge_identity();
     if (n == 0) { host_encode(R, out_fmt, out); return C25519_OK; }
-    size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32;
+    size_t psz = point_bytes(in_fmt);
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * psz + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 160 + n + 256))) return r;
     hipStream_t st = ctx->stream;
@@ -280,7 +273,7 @@ EXPORT int32_t c25519_double_and_compress_batch_dev(c25519_ctx *ctx, const uint8
     if ((r = ctx_reserve(ctx, ctx->prefix, n * 48))) return r;
     constexpr int CH = 16;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-    hipLaunchKernelGGL(k_double_compress<CH>, dim3(dup64((n + CH - 1) / CH, 256)), dim3(256), 0, ctx->stream, d_in, (uint32_t *)ctx->prefix.p, n, d_out);
+    hipLaunchKernelGGL(k_double_compress<CH>, dim3(div_up((n + CH - 1) / CH, 256)), dim3(256), 0, ctx->stream, d_in, (uint32_t *)ctx->prefix.p, n, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return C25519_OK;
@@ -288,13 +281,8 @@ EXPORT int32_t c25519_double_and_compress_batch_dev(c25519_ctx *ctx, const uint8
 EXPORT int32_t c25519_double_and_compress_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 160)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * 32))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    const ffi_in i1 = {in, d_in, 160};
-    const ffi_out o = {out, d_out, 32};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 17), &i1, 1, &o, 1,
-                        [&](uint64_t lo, uint64_t m) -> int32_t { return c25519_double_and_compress_batch_dev(ctx, d_in + lo * 160, m, d_out + lo * 32); });
+    return ffi_twin(ctx, n, 1u << 17, {{in, 160, FFI_TMP_A}}, {{out, 32, FFI_TMP_B}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_double_and_compress_batch_dev(ctx, d_in[0], m, d_out[0]); });
 }
 
 // ---- Scalar::invert_batch ------------------------------------------------------------------------------------------------
@@ -306,7 +294,7 @@ EXPORT int32_t c25519_scalar_invert_batch(c25519_ctx *ctx, uint8_t *io, uint64_t
         try {
             constexpr int CH = 16;
             const uint64_t lanes = (n + CH - 1) / CH;
-            const unsigned grid = dup64(lanes, 256);
+            const unsigned grid = div_up(lanes, 256);
             const uint64_t T = (uint64_t)grid * 256;
             int32_t r;
             if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * 40 + 64)) || (r = ctx_reserve(ctx, ctx->tmp_c, T * 40 + 64))) return r;
@@ -369,8 +357,8 @@ static int32_t on_every_context(c25519_ctx *ctx0, int32_t nctx, F &&fn) {
 EXPORT int32_t c25519_msm_vartime_multi(c25519_ctx **ctxs, int32_t nctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, int out_fmt, uint8_t *out) {
     if (!ctxs_ok(ctxs, nctx)) return -(int32_t)hipErrorInvalidValue;
     c25519_ctx *ctx = ctxs[0];
-    if (out_fmt < 0 || out_fmt > 2 || in_fmt < 0 || in_fmt > 2) { ctx->err = "msm_multi: bad format"; return -(int32_t)hipErrorInvalidValue; }
-    const size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32;
+    if (out_fmt < 0 || out_fmt > 2 || in_fmt < 0 || in_fmt > 2) return bad_arg(ctx, "msm_multi: bad format");
+    const size_t psz = point_bytes(in_fmt);
     try {
         std::vector<uint8_t> part((size_t)nctx * 160);
         std::vector<int32_t> st(nctx, C25519_OK);
@@ -398,8 +386,8 @@ EXPORT int32_t ed25519_verify_batch_multi(c25519_ctx **ctxs, int32_t nctx, const
     if (!ctxs_ok(ctxs, nctx)) return -(int32_t)hipErrorInvalidValue;
     c25519_ctx *ctx = ctxs[0];
     if (n == 0) return C25519_OK;
-    if (z_mode > 1) { ctx->err = "verify_batch_multi: bad z_mode"; return -(int32_t)hipErrorInvalidValue; }
-    for (uint64_t i = 0; i < n; i++) if (msg_off[i] > msg_off[i + 1]) { ctx->err = "verify_batch_multi: msg_off is not monotone"; return -(int32_t)hipErrorInvalidValue; }
+    if (z_mode > 1) return bad_arg(ctx, "verify_batch_multi: bad z_mode");
+    for (uint64_t i = 0; i < n; i++) if (msg_off[i] > msg_off[i + 1]) return bad_arg(ctx, "verify_batch_multi: msg_off is not monotone");
     try {
         std::vector<int32_t> st(nctx, C25519_OK);
         if (z_mode == C25519_Z_DEVICE) {

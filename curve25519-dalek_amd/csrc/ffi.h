@@ -151,3 +151,64 @@ static int32_t ffi_pipeline(c25519_ctx *ctx, uint64_t n, uint64_t chunk, const f
     const int32_t r2 = ffi_end(ctx, up_bytes, down_bytes);      // drains the copy streams on every path
     return rc ? rc : r2;
 }
+
+// ---- fixed-width host twins ---------------------------------------------------------------------------------------------------------
+// A host twin stages its arrays in the context's tmp_a / tmp_b / tmp_c only: the _dev forms keep their own workspaces (scratch, prefix,
+// tmp_c2, tmp_d, tmp_e, tmp_f), so the staging never aliases them.
+enum ffi_tmp { FFI_TMP_A, FFI_TMP_B, FFI_TMP_C };
+template <class H> struct ffi_arr {
+    H *h;                    // host array (null: not copied)
+    size_t bpu;              // bytes per unit
+    ffi_tmp buf;             // staged in this buffer, behind the arrays listed before it there (inputs before outputs)
+    size_t pad = 0;          // bytes it adds to the buffer's reservation beyond n * bpu
+    bool secret = false;     // n * bpu staged bytes zeroed after the call, on every path
+};
+using ffi_src = ffi_arr<const void>;
+using ffi_dst = ffi_arr<void>;
+
+// The twin of a _dev form whose arrays have a fixed width per unit: reserves the staging buffers (n * bytes + pads each, 16 when that
+// is 0; in the order tmp_a, tmp_b, tmp_c), registers the secret arrays for a wipe enqueued once ffi_pipeline has drained, and runs the batch
+// through ffi_pipeline in chunks of ffi_chunk_units(n, min_units) units.  compute(m, in, out) enqueues the _dev form on the m units of
+// one chunk: in[i] / out[i] are the device addresses of that chunk in the staging of ins[i] / outs[i].
+template <size_t NI, size_t NO, class F>
+static int32_t ffi_twin(c25519_ctx *ctx, uint64_t n, uint64_t min_units, const ffi_src (&ins)[NI], const ffi_dst (&outs)[NO], F &&compute) {
+    devbuf *const tmp[3] = {&ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c};
+    bool used[3] = {false, false, false};
+    size_t need[3] = {0, 0, 0}, at[3] = {0, 0, 0};
+    for (const ffi_src &a : ins) used[a.buf] = true, need[a.buf] += n * a.bpu + a.pad;
+    for (const ffi_dst &a : outs) used[a.buf] = true, need[a.buf] += n * a.bpu + a.pad;
+    for (int b = 0; b < 3; b++) {
+        const int32_t r = used[b] ? ctx_reserve(ctx, *tmp[b], need[b] ? need[b] : 16) : 0;
+        if (r) return r;
+    }
+    auto place = [&](ffi_tmp b, size_t bpu) { uint8_t *p = (uint8_t *)tmp[b]->p + at[b]; at[b] += n * bpu; return p; };
+    stream_wipe wipe(ctx->stream);
+    ffi_in in[NI];
+    ffi_out out[NO];
+    uint8_t *d_in[NI], *d_out[NO];
+    for (size_t i = 0; i < NI; i++) {
+        d_in[i] = place(ins[i].buf, ins[i].bpu);
+        in[i] = {ins[i].h, d_in[i], ins[i].bpu};
+        if (ins[i].secret) wipe.add(d_in[i], n * ins[i].bpu);
+    }
+    for (size_t i = 0; i < NO; i++) {
+        d_out[i] = place(outs[i].buf, outs[i].bpu);
+        out[i] = {outs[i].h, d_out[i], outs[i].bpu};
+        if (outs[i].secret) wipe.add(d_out[i], n * outs[i].bpu);
+    }
+    return ffi_pipeline(ctx, n, ffi_chunk_units(n, min_units), in, (int)NI, out, (int)NO, [&](uint64_t lo, uint64_t m) -> int32_t {
+        uint8_t *ci[NI], *co[NO];
+        for (size_t i = 0; i < NI; i++) ci[i] = d_in[i] + lo * ins[i].bpu;
+        for (size_t i = 0; i < NO; i++) co[i] = d_out[i] + lo * outs[i].bpu;
+        return compute(m, ci, co);
+    });
+}
+
+// ---- host twins over a message blob ---------------------------------------------------------------------------------------------------
+// The blob and its n + 1 offsets go up whole on the H2D copy stream (the kernels index the blob through the offsets), into tmp_a / tmp_b;
+// tmp_c (c_bytes) is reserved for the caller's chunked arrays, and its first c_secret bytes are registered with `wipe` (declared by the
+// caller before this call, so that it outlives the drain of a failed upload).  what: the error of non-monotone offsets.  On success the
+// copy streams have begun and ffi_pipeline(..., begun = true, m.up_bytes) takes over; on failure they have been drained.
+struct ffi_msgs { const uint8_t *d_msgs; const uint64_t *d_off; uint64_t mlen, up_bytes; };
+int32_t ffi_upload_msgs(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, const char *what, size_t c_bytes, ffi_msgs &m,
+                        stream_wipe *wipe = nullptr, size_t c_secret = 0);

@@ -8,10 +8,9 @@
 #include "devio.h"
 #include "kernels.h"
 #include "selftest.h"
+#include "capi_util.h"
 
 namespace c25519 {
-
-static inline unsigned div_up(u64 a, u64 b) { return (unsigned)((a + b - 1) / b); }
 
 // ================================================================================================
 // K3  batched compression (edwards.rs:634-647 compress_batch_alloc): Montgomery's trick

@@ -15,16 +15,9 @@
 #include "kernels.h"
 #include "ctx.h"
 #include "ffi.h"
+#include "capi_util.h"
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
-
-static inline unsigned dup64(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
 
 namespace c25519 {
 
@@ -89,39 +82,34 @@ __global__ void __launch_bounds__(256) k_edwards_h2c(const uint8_t *__restrict__
 
 }  // namespace c25519
 
-static int32_t h2c_bad_fmt(c25519_ctx *ctx, const char *what) { ctx->err = what; return -(int32_t)hipErrorInvalidValue; }
-static bool ris_fmt_ok(int f) { return f == C25519_FMT_RISTRETTO || f == C25519_FMT_RAW160; }
-static bool ed_fmt_ok(int f) { return f == C25519_FMT_EDWARDS_Y || f == C25519_FMT_RAW160; }
-static size_t fmt_bytes(int f) { return f == C25519_FMT_RAW160 ? 160 : 32; }
-
 // bad offsets flagged by a hashing kernel -> error, like verify_batch / sign_batch.  Synchronises the context's stream.
 static int32_t h2c_offsets_verdict(c25519_ctx *ctx, const char *what) {
     uint32_t fl[4] = {0, 0, 0, 0};
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpy(fl, ctx->d_flag, 16, hipMemcpyDeviceToHost));
-    if (fl[1]) { ctx->err = what; return -(int32_t)hipErrorInvalidValue; }
+    if (fl[1]) return bad_arg(ctx, what);
     return C25519_OK;
 }
 
 // ---- Ristretto from_uniform_bytes / map_to_curve ---------------------------------------------------------------------------
 EXPORT int32_t c25519_ristretto_from_uniform_bytes_batch_dev(c25519_ctx *ctx, const uint8_t *d_in64, uint64_t n, int out_fmt, uint8_t *d_out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ris_fmt_ok(out_fmt)) return h2c_bad_fmt(ctx, "ristretto_from_uniform_bytes: out_fmt must be 1 or 2");
+    if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, "ristretto_from_uniform_bytes: out_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-    if (out_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_ristretto_from_uniform<H2C_OUT_RIS>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_in64, n, d_out);
-    else hipLaunchKernelGGL(k_ristretto_from_uniform<H2C_OUT_RAW>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_in64, n, d_out);
+    if (out_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_ristretto_from_uniform<H2C_OUT_RIS>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_in64, n, d_out);
+    else hipLaunchKernelGGL(k_ristretto_from_uniform<H2C_OUT_RAW>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_in64, n, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return C25519_OK;
 }
 EXPORT int32_t c25519_ristretto_map_to_curve_batch_dev(c25519_ctx *ctx, const uint8_t *d_in32, uint64_t n, int out_fmt, uint8_t *d_out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ris_fmt_ok(out_fmt)) return h2c_bad_fmt(ctx, "ristretto_map_to_curve: out_fmt must be 1 or 2");
+    if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, "ristretto_map_to_curve: out_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-    if (out_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_ristretto_map<H2C_OUT_RIS>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_in32, n, d_out);
-    else hipLaunchKernelGGL(k_ristretto_map<H2C_OUT_RAW>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_in32, n, d_out);
+    if (out_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_ristretto_map<H2C_OUT_RIS>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_in32, n, d_out);
+    else hipLaunchKernelGGL(k_ristretto_map<H2C_OUT_RAW>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_in32, n, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return C25519_OK;
@@ -130,16 +118,10 @@ EXPORT int32_t c25519_ristretto_map_to_curve_batch_dev(c25519_ctx *ctx, const ui
 static int32_t ris_fixed_host(c25519_ctx *ctx, const uint8_t *in, size_t in_bytes, uint64_t n, int out_fmt, uint8_t *out,
                               int32_t (*dev)(c25519_ctx *, const uint8_t *, uint64_t, int, uint8_t *), const char *what) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ris_fmt_ok(out_fmt)) return h2c_bad_fmt(ctx, what);
+    if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, what);
     if (n == 0) return C25519_OK;
-    const size_t ob = fmt_bytes(out_fmt);
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * in_bytes)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * ob))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    const ffi_in i1 = {in, d_in, in_bytes};
-    const ffi_out o = {out, d_out, ob};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 16), &i1, 1, &o, 1,
-                        [&](uint64_t lo, uint64_t m) -> int32_t { return dev(ctx, d_in + lo * in_bytes, m, out_fmt, d_out + lo * ob); });
+    return ffi_twin(ctx, n, 1u << 16, {{in, in_bytes, FFI_TMP_A}}, {{out, point_bytes(out_fmt), FFI_TMP_B}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return dev(ctx, d_in[0], m, out_fmt, d_out[0]); });
 }
 EXPORT int32_t c25519_ristretto_from_uniform_bytes_batch(c25519_ctx *ctx, const uint8_t *in64, uint64_t n, int out_fmt, uint8_t *out) {
     return ris_fixed_host(ctx, in64, 64, n, out_fmt, out, c25519_ristretto_from_uniform_bytes_batch_dev, "ristretto_from_uniform_bytes: out_fmt must be 1 or 2");
@@ -152,14 +134,14 @@ EXPORT int32_t c25519_ristretto_map_to_curve_batch(c25519_ctx *ctx, const uint8_
 EXPORT int32_t c25519_ristretto_hash_from_bytes_batch_dev(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len, uint64_t n,
                                                           int out_fmt, uint8_t *d_out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ris_fmt_ok(out_fmt)) return h2c_bad_fmt(ctx, "ristretto_hash_from_bytes: out_fmt must be 1 or 2");
+    if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, "ristretto_hash_from_bytes: out_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
     HIPCHK(hipMemsetAsync(ctx->d_flag, 0, 16, ctx->stream));
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     uint32_t *fl = (uint32_t *)ctx->d_flag;
     if (out_fmt == C25519_FMT_RISTRETTO)
-        hipLaunchKernelGGL(k_ristretto_hash<H2C_OUT_RIS>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_msgs, d_msg_off, msgs_len, n, fl, d_out);
-    else hipLaunchKernelGGL(k_ristretto_hash<H2C_OUT_RAW>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_msgs, d_msg_off, msgs_len, n, fl, d_out);
+        hipLaunchKernelGGL(k_ristretto_hash<H2C_OUT_RIS>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_msgs, d_msg_off, msgs_len, n, fl, d_out);
+    else hipLaunchKernelGGL(k_ristretto_hash<H2C_OUT_RAW>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_msgs, d_msg_off, msgs_len, n, fl, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return h2c_offsets_verdict(ctx, "ristretto_hash_from_bytes: msg_off is not monotone or runs past msgs_len");
@@ -168,7 +150,7 @@ EXPORT int32_t c25519_ristretto_hash_from_bytes_batch_dev(c25519_ctx *ctx, const
 // DST (a HOST pointer, 1 .. 255 bytes) into the context's small device buffer; the host copy stays in the context until the next call
 static int32_t dst_upload(c25519_ctx *ctx, const uint8_t *dst, uint32_t dst_len) {
     if (dst_len == 0 || dst_len > 255) { ctx->err = "hash_to_curve: the domain separator must have 1 .. 255 bytes"; return C25519_DOMAIN_SEPARATOR_LENGTH; }
-    if (!dst) { ctx->err = "hash_to_curve: null domain separator"; return -(int32_t)hipErrorInvalidValue; }
+    if (!dst) return bad_arg(ctx, "hash_to_curve: null domain separator");
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->dom, 512))) return r;
     ctx->h_dom.assign(dst, dst + dst_len);
@@ -179,8 +161,8 @@ EXPORT int32_t c25519_edwards_hash_to_curve_batch_dev(c25519_ctx *ctx, const uin
                                                       const uint8_t *dst, uint32_t dst_len, int mode, int out_fmt, uint8_t *d_out) {
     HIPCHK(hipSetDevice(ctx->device));
     if (dst_len == 0 || dst_len > 255) { ctx->err = "hash_to_curve: the domain separator must have 1 .. 255 bytes"; return C25519_DOMAIN_SEPARATOR_LENGTH; }
-    if (mode != C25519_H2C_RO && mode != C25519_H2C_NU) return h2c_bad_fmt(ctx, "hash_to_curve: mode must be C25519_H2C_RO or C25519_H2C_NU");
-    if (!ed_fmt_ok(out_fmt)) return h2c_bad_fmt(ctx, "hash_to_curve: out_fmt must be 0 or 2");
+    if (mode != C25519_H2C_RO && mode != C25519_H2C_NU) return bad_arg(ctx, "hash_to_curve: mode must be C25519_H2C_RO or C25519_H2C_NU");
+    if (!ed_fmt_ok(out_fmt)) return bad_arg(ctx, "hash_to_curve: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
     int32_t r;
     if ((r = dst_upload(ctx, dst, dst_len))) return r;
@@ -194,7 +176,7 @@ EXPORT int32_t c25519_edwards_hash_to_curve_batch_dev(c25519_ctx *ctx, const uin
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     const uint8_t *d_dst = (const uint8_t *)ctx->dom.p;
     uint32_t *fl = (uint32_t *)ctx->d_flag;
-#define H2C_LAUNCH(RO_, OUT_) hipLaunchKernelGGL((k_edwards_h2c<RO_, OUT_>), dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_msgs, d_msg_off, msgs_len, d_dst, dst_len, n, fl, dest)
+#define H2C_LAUNCH(RO_, OUT_) hipLaunchKernelGGL((k_edwards_h2c<RO_, OUT_>), dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_msgs, d_msg_off, msgs_len, d_dst, dst_len, n, fl, dest)
     if (ro) { if (raw) H2C_LAUNCH(true, H2C_OUT_RAW); else H2C_LAUNCH(true, H2C_OUT_P32); }
     else { if (raw) H2C_LAUNCH(false, H2C_OUT_RAW); else H2C_LAUNCH(false, H2C_OUT_P32); }
 #undef H2C_LAUNCH
@@ -208,25 +190,18 @@ EXPORT int32_t c25519_edwards_hash_to_curve_batch_dev(c25519_ctx *ctx, const uin
 // host twins: messages and offsets up as whole arrays, one chunk (the _dev form reads its offsets flag back)
 template <class F>
 static int32_t h2c_msgs_host(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, int out_fmt, uint8_t *out, const char *what, F &&dev) {
-    for (uint64_t i = 0; i < n; i++) if (msg_off[i] > msg_off[i + 1]) { ctx->err = what; return -(int32_t)hipErrorInvalidValue; }
-    const uint64_t mlen = msg_off[n];
-    const size_t ob = fmt_bytes(out_fmt);
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, mlen + 64)) || (r = ctx_reserve(ctx, ctx->tmp_b, (n + 1) * 8)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * ob))) return r;
-    uint8_t *dmsg = (uint8_t *)ctx->tmp_a.p, *dout = (uint8_t *)ctx->tmp_c.p;
-    uint64_t *doff = (uint64_t *)ctx->tmp_b.p;
-    if ((r = ffi_begin(ctx))) return r;
-    ffi_guard guard(ctx);
-    if (mlen) HIPCHK(hipMemcpyAsync(dmsg, msgs, mlen, hipMemcpyHostToDevice, ctx->s_h2d));
-    HIPCHK(hipMemcpyAsync(doff, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_h2d));
+    const size_t ob = point_bytes(out_fmt);
+    ffi_msgs mm;
+    const int32_t r = ffi_upload_msgs(ctx, msgs, msg_off, n, what, n * ob, mm);
+    if (r) return r;
+    uint8_t *dout = (uint8_t *)ctx->tmp_c.p;
     const ffi_out o = {out, dout, ob};
-    guard.dismiss();
-    return ffi_pipeline(ctx, n, n, nullptr, 0, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t { return dev(dmsg, doff + lo, mlen, m, dout + lo * ob); },
-                        true, mlen + (n + 1) * 8);
+    return ffi_pipeline(ctx, n, n, nullptr, 0, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t { return dev(mm.d_msgs, mm.d_off + lo, mm.mlen, m, dout + lo * ob); },
+                        true, mm.up_bytes);
 }
 EXPORT int32_t c25519_ristretto_hash_from_bytes_batch(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, int out_fmt, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ris_fmt_ok(out_fmt)) return h2c_bad_fmt(ctx, "ristretto_hash_from_bytes: out_fmt must be 1 or 2");
+    if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, "ristretto_hash_from_bytes: out_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
     return h2c_msgs_host(ctx, msgs, msg_off, n, out_fmt, out, "ristretto_hash_from_bytes: msg_off is not monotone",
                          [&](const uint8_t *dm, const uint64_t *doff, uint64_t mlen, uint64_t m, uint8_t *dout) {
@@ -237,8 +212,8 @@ EXPORT int32_t c25519_edwards_hash_to_curve_batch(c25519_ctx *ctx, const uint8_t
                                                   int mode, int out_fmt, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
     if (dst_len == 0 || dst_len > 255) { ctx->err = "hash_to_curve: the domain separator must have 1 .. 255 bytes"; return C25519_DOMAIN_SEPARATOR_LENGTH; }
-    if (mode != C25519_H2C_RO && mode != C25519_H2C_NU) return h2c_bad_fmt(ctx, "hash_to_curve: mode must be C25519_H2C_RO or C25519_H2C_NU");
-    if (!ed_fmt_ok(out_fmt)) return h2c_bad_fmt(ctx, "hash_to_curve: out_fmt must be 0 or 2");
+    if (mode != C25519_H2C_RO && mode != C25519_H2C_NU) return bad_arg(ctx, "hash_to_curve: mode must be C25519_H2C_RO or C25519_H2C_NU");
+    if (!ed_fmt_ok(out_fmt)) return bad_arg(ctx, "hash_to_curve: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
     return h2c_msgs_host(ctx, msgs, msg_off, n, out_fmt, out, "hash_to_curve: msg_off is not monotone",
                          [&](const uint8_t *dm, const uint64_t *doff, uint64_t mlen, uint64_t m, uint8_t *dout) {

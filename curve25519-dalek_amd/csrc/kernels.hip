@@ -8,6 +8,7 @@
 #include "fe26x.h"
 #include "knobs.h"
 #include "montgomery.h"
+#include "capi_util.h"
 #ifndef C25519_PREPC_ATTR
 #define C25519_PREPC_ATTR
 #endif
@@ -698,7 +699,6 @@ __global__ void __launch_bounds__(256) k_prep_compressed_keys_and_r(const uint8_
 // ================================================================================================
 // launchers
 // ================================================================================================
-static inline unsigned div_up(u64 a, u64 b) { return (unsigned)((a + b - 1) / b); }
 hipError_t launch_prep_compressed_keys_and_r(const uint8_t *pks, const uint8_t *sigs, uint64_t n, uint32_t *pts, uint32_t *bad_count, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_prep_compressed_keys_and_r, dim3(div_up(2 * n, 256)), dim3(256), 0, st, pks, sigs, n, pts, bad_count);

@@ -13,16 +13,9 @@
 #include "lizard.h"
 #include "ctx.h"
 #include "ffi.h"
+#include "capi_util.h"
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
-
-static inline unsigned dup64(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
 
 namespace c25519 {
 
@@ -96,29 +89,25 @@ __global__ void __launch_bounds__(256) k_map_to_curve_inverse(const uint8_t *__r
 
 }  // namespace c25519
 
-static int32_t lz_bad_fmt(c25519_ctx *ctx, const char *what) { ctx->err = what; return -(int32_t)hipErrorInvalidValue; }
-static bool lz_fmt_ok(int f) { return f == C25519_FMT_RISTRETTO || f == C25519_FMT_RAW160; }
-static size_t lz_fmt_bytes(int f) { return f == C25519_FMT_RAW160 ? 160 : 32; }
-
 // ---- _dev forms --------------------------------------------------------------------------------------------------------------
 EXPORT int32_t c25519_ristretto_lizard_encode_sha256_batch_dev(c25519_ctx *ctx, const uint8_t *d_data16, uint64_t n, int out_fmt, uint8_t *d_out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!lz_fmt_ok(out_fmt)) return lz_bad_fmt(ctx, "ristretto_lizard_encode: out_fmt must be 1 or 2");
+    if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, "ristretto_lizard_encode: out_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-    if (out_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_lizard_encode<LZ_RIS>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_data16, n, d_out);
-    else hipLaunchKernelGGL(k_lizard_encode<LZ_RAW>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_data16, n, d_out);
+    if (out_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_lizard_encode<LZ_RIS>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_data16, n, d_out);
+    else hipLaunchKernelGGL(k_lizard_encode<LZ_RAW>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_data16, n, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return C25519_OK;
 }
 EXPORT int32_t c25519_ristretto_lizard_decode_sha256_batch_dev(c25519_ctx *ctx, const uint8_t *d_in, uint64_t n, int in_fmt, uint8_t *d_out16, uint8_t *d_status) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!lz_fmt_ok(in_fmt)) return lz_bad_fmt(ctx, "ristretto_lizard_decode: in_fmt must be 1 or 2");
+    if (!ris_fmt_ok(in_fmt)) return bad_arg(ctx, "ristretto_lizard_decode: in_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
-    if (in_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_lizard_decode<LZ_RIS>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_in, n, d_out16, d_status);
-    else hipLaunchKernelGGL(k_lizard_decode<LZ_RAW>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_in, n, d_out16, d_status);
+    if (in_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_lizard_decode<LZ_RIS>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_in, n, d_out16, d_status);
+    else hipLaunchKernelGGL(k_lizard_decode<LZ_RAW>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_in, n, d_out16, d_status);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return C25519_OK;
@@ -126,13 +115,13 @@ EXPORT int32_t c25519_ristretto_lizard_decode_sha256_batch_dev(c25519_ctx *ctx, 
 EXPORT int32_t c25519_ristretto_map_to_curve_inverse_batch_dev(c25519_ctx *ctx, const uint8_t *d_in, uint64_t n, int in_fmt, uint8_t *d_out512, uint16_t *d_mask,
                                                                uint8_t *d_ok) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!lz_fmt_ok(in_fmt)) return lz_bad_fmt(ctx, "ristretto_map_to_curve_inverse: in_fmt must be 1 or 2");
+    if (!ris_fmt_ok(in_fmt)) return bad_arg(ctx, "ristretto_map_to_curve_inverse: in_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
-    if (in_fmt == C25519_FMT_RISTRETTO && !d_ok) return lz_bad_fmt(ctx, "ristretto_map_to_curve_inverse: d_ok may be NULL for RAW160 input only");
+    if (in_fmt == C25519_FMT_RISTRETTO && !d_ok) return bad_arg(ctx, "ristretto_map_to_curve_inverse: d_ok may be NULL for RAW160 input only");
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     if (in_fmt == C25519_FMT_RISTRETTO)
-        hipLaunchKernelGGL(k_map_to_curve_inverse<LZ_RIS>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_in, n, d_out512, d_mask, d_ok);
-    else hipLaunchKernelGGL(k_map_to_curve_inverse<LZ_RAW>, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_in, n, d_out512, d_mask, d_ok);
+        hipLaunchKernelGGL(k_map_to_curve_inverse<LZ_RIS>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_in, n, d_out512, d_mask, d_ok);
+    else hipLaunchKernelGGL(k_map_to_curve_inverse<LZ_RAW>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_in, n, d_out512, d_mask, d_ok);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return C25519_OK;
@@ -141,49 +130,28 @@ EXPORT int32_t c25519_ristretto_map_to_curve_inverse_batch_dev(c25519_ctx *ctx, 
 // ---- host twins: chunked through the copy streams (ffi.h) ----------------------------------------------------------------------
 EXPORT int32_t c25519_ristretto_lizard_encode_sha256_batch(c25519_ctx *ctx, const uint8_t *data16, uint64_t n, int out_fmt, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!lz_fmt_ok(out_fmt)) return lz_bad_fmt(ctx, "ristretto_lizard_encode: out_fmt must be 1 or 2");
+    if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, "ristretto_lizard_encode: out_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
-    const size_t ob = lz_fmt_bytes(out_fmt);
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * ob))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    const ffi_in i1 = {data16, d_in, 16};
-    const ffi_out o = {out, d_out, ob};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 16), &i1, 1, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return c25519_ristretto_lizard_encode_sha256_batch_dev(ctx, d_in + lo * 16, m, out_fmt, d_out + lo * ob);
-    });
+    return ffi_twin(ctx, n, 1u << 16, {{data16, 16, FFI_TMP_A}}, {{out, point_bytes(out_fmt), FFI_TMP_B}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_ristretto_lizard_encode_sha256_batch_dev(ctx, d_in[0], m, out_fmt, d_out[0]); });
 }
 EXPORT int32_t c25519_ristretto_lizard_decode_sha256_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int in_fmt, uint8_t *out16, uint8_t *status) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!lz_fmt_ok(in_fmt)) return lz_bad_fmt(ctx, "ristretto_lizard_decode: in_fmt must be 1 or 2");
+    if (!ris_fmt_ok(in_fmt)) return bad_arg(ctx, "ristretto_lizard_decode: in_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
-    const size_t ib = lz_fmt_bytes(in_fmt);
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * ib)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, n))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p, *d_st = (uint8_t *)ctx->tmp_c.p;
-    const ffi_in i1 = {in, d_in, ib};
-    const ffi_out o[2] = {{out16, d_out, 16}, {status, d_st, 1}};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 16), &i1, 1, o, 2, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return c25519_ristretto_lizard_decode_sha256_batch_dev(ctx, d_in + lo * ib, m, in_fmt, d_out + lo * 16, d_st + lo);
-    });
+    return ffi_twin(ctx, n, 1u << 16, {{in, point_bytes(in_fmt), FFI_TMP_A}}, {{out16, 16, FFI_TMP_B}, {status, 1, FFI_TMP_C}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_ristretto_lizard_decode_sha256_batch_dev(ctx, d_in[0], m, in_fmt, d_out[0], d_out[1]); });
 }
 EXPORT int32_t c25519_ristretto_map_to_curve_inverse_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int in_fmt, uint8_t *out512, uint16_t *mask,
                                                            uint8_t *ok) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!lz_fmt_ok(in_fmt)) return lz_bad_fmt(ctx, "ristretto_map_to_curve_inverse: in_fmt must be 1 or 2");
+    if (!ris_fmt_ok(in_fmt)) return bad_arg(ctx, "ristretto_map_to_curve_inverse: in_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
-    if (in_fmt == C25519_FMT_RISTRETTO && !ok) return lz_bad_fmt(ctx, "ristretto_map_to_curve_inverse: ok may be NULL for RAW160 input only");
-    const size_t ib = lz_fmt_bytes(in_fmt);
+    if (in_fmt == C25519_FMT_RISTRETTO && !ok) return bad_arg(ctx, "ristretto_map_to_curve_inverse: ok may be NULL for RAW160 input only");
     const bool want_ok = ok != nullptr && in_fmt == C25519_FMT_RISTRETTO;
-    int32_t r;
-    // tmp_c: the n uint16 masks, then the n validity bytes
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * ib)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * 512)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 3))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    uint16_t *d_mask = (uint16_t *)ctx->tmp_c.p;
-    uint8_t *d_ok = (uint8_t *)ctx->tmp_c.p + 2 * n;
-    const ffi_in i1 = {in, d_in, ib};
-    const ffi_out o[3] = {{out512, d_out, 512}, {mask, d_mask, 2}, {ok, d_ok, 1}};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 14), &i1, 1, o, want_ok ? 3 : 2, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return c25519_ristretto_map_to_curve_inverse_batch_dev(ctx, d_in + lo * ib, m, in_fmt, d_out + lo * 512, d_mask + lo, want_ok ? d_ok + lo : nullptr);
-    });
+    // tmp_c: the n uint16 masks, then the n validity bytes (staged, not copied back, when unused)
+    return ffi_twin(ctx, n, 1u << 14, {{in, point_bytes(in_fmt), FFI_TMP_A}}, {{out512, 512, FFI_TMP_B}, {mask, 2, FFI_TMP_C}, {want_ok ? ok : nullptr, 1, FFI_TMP_C}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) {
+                        return c25519_ristretto_map_to_curve_inverse_batch_dev(ctx, d_in[0], m, in_fmt, d_out[0], (uint16_t *)d_out[1], want_ok ? d_out[2] : nullptr);
+                    });
 }

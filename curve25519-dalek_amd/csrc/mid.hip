@@ -42,13 +42,9 @@
 #include "msm_sort.h"
 #include "fe26x.h"
 #include "mid_long.h"
+#include "capi_util.h"
 
 using namespace c25519;
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
 
 namespace c25519 {
 
@@ -439,8 +435,8 @@ int32_t msm_mid_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const void *p
     // (profiles/r06_timeline_mid_verify_2p15_long_cap.txt).  One wave per 256 entries handles such a list in ~30 us.
     msm_geom g = g_in;
     g.long_cap = mid_pick_cap(n, g, (u32)std::max<uint64_t>(48, 3 * (n / (uint64_t)g.half + 1)), src_fmt != 0);
-    if (!msm_mid_serves(n, g, src_fmt != 0) || n >= (1ull << 31)) { ctx->err = "msm: internal error (mid path outside its range)"; return -(int32_t)hipErrorInvalidValue; }
-    if (run && src_fmt == 0) { ctx->err = "msm: internal error (mid path: a stream override with raw points)"; return -(int32_t)hipErrorInvalidValue; }
+    if (!msm_mid_serves(n, g, src_fmt != 0) || n >= (1ull << 31)) return bad_arg(ctx, "msm: internal error (mid path outside its range)");
+    if (run && src_fmt == 0) return bad_arg(ctx, "msm: internal error (mid path: a stream override with raw points)");
     hipStream_t st = run && run->stream ? run->stream : ctx->stream;
     const uint64_t dstride = (n + 7) & ~(uint64_t)7;
     const uint64_t nb = (uint64_t)g.nwin * g.half;

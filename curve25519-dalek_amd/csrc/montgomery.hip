@@ -18,16 +18,9 @@
 #include "knobs.h"
 #include "ctx.h"
 #include "ffi.h"
+#include "capi_util.h"
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
-
-static inline unsigned dup64(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
 
 namespace c25519 {
 
@@ -130,10 +123,6 @@ __global__ void __launch_bounds__(256) k_mont_to_edwards(const uint8_t *__restri
 
 }  // namespace c25519
 
-static int32_t mt_bad(c25519_ctx *ctx, const char *what) { ctx->err = what; return -(int32_t)hipErrorInvalidValue; }
-static bool te_fmt_ok(int f) { return f == C25519_FMT_EDWARDS_Y || f == C25519_FMT_RAW160; }
-static inline int32_t reserve2(c25519_ctx *ctx, devbuf &a, size_t na, devbuf &b, size_t nb) { int32_t r = ctx_reserve(ctx, a, na ? na : 16); return r ? r : ctx_reserve(ctx, b, nb ? nb : 16); }
-
 // ---- _dev forms --------------------------------------------------------------------------------------------------------------
 // the ladder kernel, then U / W batched; scratch / prefix hold secret-derived values and are wiped on every exit path
 template <class L>
@@ -158,16 +147,16 @@ EXPORT int32_t c25519_montgomery_mul_batch_dev(c25519_ctx *ctx, const uint8_t *d
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
     return ladder_dev(ctx, n, d_out, "c25519::k_mont_mul", [&](uint32_t *scratch) {
-        hipLaunchKernelGGL(k_mont_mul, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_k, d_u, n, scratch);
+        hipLaunchKernelGGL(k_mont_mul, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_k, d_u, n, scratch);
     });
 }
 EXPORT int32_t c25519_montgomery_mul_bits_be_batch_dev(c25519_ctx *ctx, const uint8_t *d_bits, uint32_t nbits, const uint8_t *d_u, uint64_t n, uint8_t *d_out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (nbits > C25519_MONTGOMERY_MAX_BITS) return mt_bad(ctx, "montgomery_mul_bits_be: nbits must be at most 512");
+    if (nbits > C25519_MONTGOMERY_MAX_BITS) return bad_arg(ctx, "montgomery_mul_bits_be: nbits must be at most 512");
     if (n == 0) return C25519_OK;
     const uint32_t nb = (nbits + 7) / 8;
     return ladder_dev(ctx, n, d_out, "c25519::k_mont_mul_bits", [&](uint32_t *scratch) {
-        hipLaunchKernelGGL(k_mont_mul_bits, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_bits, nbits, nb, d_u, n, scratch);
+        hipLaunchKernelGGL(k_mont_mul_bits, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_bits, nbits, nb, d_u, n, scratch);
     });
 }
 // fixed base, unclamped: c25519_x25519_base_batch_dev without the clamp (constant-time tables unless C25519_FLAG_VARTIME_TABLES)
@@ -192,7 +181,7 @@ EXPORT int32_t c25519_montgomery_mul_base_batch_dev(c25519_ctx *ctx, const uint8
 EXPORT int32_t c25519_montgomery_to_edwards_batch_dev(c25519_ctx *ctx, const uint8_t *d_u, const uint8_t *d_signs, uint64_t n, int out_fmt, uint8_t *d_out,
                                                       uint8_t *d_status) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!te_fmt_ok(out_fmt)) return mt_bad(ctx, "montgomery_to_edwards: out_fmt must be 0 or 2");
+    if (!ed_fmt_ok(out_fmt)) return bad_arg(ctx, "montgomery_to_edwards: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
     // y through the batched division of k_ratio_p32 (one inversion per 16 items): 0.98 ms at 2^20 against 1.52 ms with one fe_invert per lane,
     // which stays as the A/B arm (knob 0, tuning build only; DESIGN.md §3.10, profiles/montgomery_numbers.txt)
@@ -204,12 +193,12 @@ EXPORT int32_t c25519_montgomery_to_edwards_batch_dev(c25519_ctx *ctx, const uin
     }
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     if (batched) {
-        hipLaunchKernelGGL(k_mont_to_edwards_prep, dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_u, n, (uint32_t *)ctx->scratch.p);
+        hipLaunchKernelGGL(k_mont_to_edwards_prep, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_u, n, (uint32_t *)ctx->scratch.p);
         HIPCHK(hipGetLastError());
         HIPCHK(launch_ratio_p32(0, (const uint32_t *)ctx->scratch.p, (uint32_t *)ctx->prefix.p, n, (uint8_t *)ctx->tmp_e.p, ctx->stream));
         ybuf = (const uint8_t *)ctx->tmp_e.p;
     }
-#define C25519_TE(OUT, B) hipLaunchKernelGGL((k_mont_to_edwards<OUT, B>), dim3(dup64(n, 256)), dim3(256), 0, ctx->stream, d_u, d_signs, ybuf, n, d_out, d_status)
+#define C25519_TE(OUT, B) hipLaunchKernelGGL((k_mont_to_edwards<OUT, B>), dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_u, d_signs, ybuf, n, d_out, d_status)
     if (out_fmt == C25519_FMT_EDWARDS_Y) { if (batched) C25519_TE(TE_Y, true); else C25519_TE(TE_Y, false); }
     else { if (batched) C25519_TE(TE_RAW, true); else C25519_TE(TE_RAW, false); }
 #undef C25519_TE
@@ -222,58 +211,29 @@ EXPORT int32_t c25519_montgomery_to_edwards_batch_dev(c25519_ctx *ctx, const uin
 EXPORT int32_t c25519_montgomery_mul_batch(c25519_ctx *ctx, const uint8_t *k, const uint8_t *u, uint64_t n, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
-    int32_t r;
-    if ((r = reserve2(ctx, ctx->tmp_a, n * 32, ctx->tmp_b, n * 32)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 32))) return r;
-    uint8_t *d_k = (uint8_t *)ctx->tmp_a.p, *d_u = (uint8_t *)ctx->tmp_b.p, *d_out = (uint8_t *)ctx->tmp_c.p;
-    stream_wipe wipe(ctx->stream);
-    wipe.add(d_k, n * 32);                                // the staged scalars
-    const ffi_in in[2] = {{k, d_k, 32}, {u, d_u, 32}};
-    const ffi_out o = {out, d_out, 32};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 17), in, 2, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return c25519_montgomery_mul_batch_dev(ctx, d_k + lo * 32, d_u + lo * 32, m, d_out + lo * 32);
-    });
+    return ffi_twin(ctx, n, 1u << 17, {{k, 32, FFI_TMP_A, 0, true}, {u, 32, FFI_TMP_B}}, {{out, 32, FFI_TMP_C}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_montgomery_mul_batch_dev(ctx, d_in[0], d_in[1], m, d_out[0]); });
 }
 EXPORT int32_t c25519_montgomery_mul_bits_be_batch(c25519_ctx *ctx, const uint8_t *bits, uint32_t nbits, const uint8_t *u, uint64_t n, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (nbits > C25519_MONTGOMERY_MAX_BITS) return mt_bad(ctx, "montgomery_mul_bits_be: nbits must be at most 512");
+    if (nbits > C25519_MONTGOMERY_MAX_BITS) return bad_arg(ctx, "montgomery_mul_bits_be: nbits must be at most 512");
     if (n == 0) return C25519_OK;
     const size_t nb = (nbits + 7) / 8;
-    int32_t r;
-    if ((r = reserve2(ctx, ctx->tmp_a, n * nb + 16, ctx->tmp_b, n * 32)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 32))) return r;
-    uint8_t *d_bits = (uint8_t *)ctx->tmp_a.p, *d_u = (uint8_t *)ctx->tmp_b.p, *d_out = (uint8_t *)ctx->tmp_c.p;
-    stream_wipe wipe(ctx->stream);
-    wipe.add(d_bits, n * nb);                             // the staged bits
-    const ffi_in in[2] = {{u, d_u, 32}, {bits, d_bits, nb}};
-    const ffi_out o = {out, d_out, 32};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 17), in, nb ? 2 : 1, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return c25519_montgomery_mul_bits_be_batch_dev(ctx, d_bits + lo * nb, nbits, d_u + lo * 32, m, d_out + lo * 32);
-    });
+    // the staged bits are wiped; with nbits = 0 there is nothing to copy
+    return ffi_twin(ctx, n, 1u << 17, {{u, 32, FFI_TMP_B}, {nb ? bits : nullptr, nb, FFI_TMP_A, 16, true}}, {{out, 32, FFI_TMP_C}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_montgomery_mul_bits_be_batch_dev(ctx, d_in[1], nbits, d_in[0], m, d_out[0]); });
 }
 EXPORT int32_t c25519_montgomery_mul_base_batch(c25519_ctx *ctx, const uint8_t *scalars, uint64_t n, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
-    int32_t r;
-    if ((r = reserve2(ctx, ctx->tmp_a, n * 32, ctx->tmp_b, n * 32))) return r;
-    uint8_t *d_in = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p;
-    stream_wipe wipe(ctx->stream);
-    wipe.add(d_in, n * 32);                               // the staged secrets
-    const ffi_in in = {scalars, d_in, 32};
-    const ffi_out o = {out, d_out, 32};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 18), &in, 1, &o, 1,
-                        [&](uint64_t lo, uint64_t m) -> int32_t { return c25519_montgomery_mul_base_batch_dev(ctx, d_in + lo * 32, m, d_out + lo * 32); });
+    return ffi_twin(ctx, n, 1u << 18, {{scalars, 32, FFI_TMP_A, 0, true}}, {{out, 32, FFI_TMP_B}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_montgomery_mul_base_batch_dev(ctx, d_in[0], m, d_out[0]); });
 }
 EXPORT int32_t c25519_montgomery_to_edwards_batch(c25519_ctx *ctx, const uint8_t *u, const uint8_t *signs, uint64_t n, int out_fmt, uint8_t *out, uint8_t *status) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!te_fmt_ok(out_fmt)) return mt_bad(ctx, "montgomery_to_edwards: out_fmt must be 0 or 2");
+    if (!ed_fmt_ok(out_fmt)) return bad_arg(ctx, "montgomery_to_edwards: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
-    const size_t ob = out_fmt == C25519_FMT_RAW160 ? 160 : 32;
-    int32_t r;
     // tmp_c: the n sign bytes, then the n status bytes
-    if ((r = reserve2(ctx, ctx->tmp_a, n * 32, ctx->tmp_b, n * ob)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 2))) return r;
-    uint8_t *d_u = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_b.p, *d_sg = (uint8_t *)ctx->tmp_c.p, *d_st = d_sg + n;
-    const ffi_in in[2] = {{u, d_u, 32}, {signs, d_sg, 1}};
-    const ffi_out o[2] = {{out, d_out, ob}, {status, d_st, 1}};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 17), in, 2, o, 2, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return c25519_montgomery_to_edwards_batch_dev(ctx, d_u + lo * 32, d_sg + lo, m, out_fmt, d_out + lo * ob, d_st + lo);
-    });
+    return ffi_twin(ctx, n, 1u << 17, {{u, 32, FFI_TMP_A}, {signs, 1, FFI_TMP_C}}, {{out, point_bytes(out_fmt), FFI_TMP_B}, {status, 1, FFI_TMP_C}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_montgomery_to_edwards_batch_dev(ctx, d_in[0], d_in[1], m, out_fmt, d_out[0], d_out[1]); });
 }

@@ -44,15 +44,10 @@
 #include "msm_sort.h"
 #include "host51.h"
 #include "ffi.h"
+#include "capi_util.h"
 #include <functional>
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
 
 namespace c25519 {
 
@@ -562,7 +557,7 @@ EXPORT int32_t c25519_msm_geometry(uint64_t n, int32_t *c, int32_t *nwin, uint8_
 // stream -- for kernel traces of the sort without an accumulation beside it (tools/sort_only.py)
 EXPORT int32_t c25519_debug_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, uint64_t layout_terms, int32_t reps) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (n <= msm_small_max() || n > (1ull << 22)) { ctx->err = "debug_sort: n outside the range of a bucket-method pass"; return -(int32_t)hipErrorInvalidValue; }
+    if (n <= msm_small_max() || n > (1ull << 22)) return bad_arg(ctx, "debug_sort: n outside the range of a bucket-method pass");
     msm_geom g;
     msm_layout(layout_terms ? layout_terms : n, g);
     for (int i = 0; i < reps; i++) {
@@ -599,7 +594,7 @@ int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_plan &pl, const uint32_t *d_p
                         const uint32_t *d_bad_sticky) {
     const msm_geom &g = pl.g;
     // (k_accumulate's gathers address a record by a 32-bit byte offset from the pass's base: 2^25 records of 128 bytes.  The sorts' entries hold 23- / 24-bit ids.)
-    if (pl.n > (1ull << 25)) { ctx->err = "msm: internal error (a pass of more than 2^25 records)"; return -(int32_t)hipErrorInvalidValue; }
+    if (pl.n > (1ull << 25)) return bad_arg(ctx, "msm: internal error (a pass of more than 2^25 records)");
     if (pl.sort_stream && pl.sort_stream != ctx->stream) {                // join: the main stream continues once the lists exist
         HIPCHK(hipEventRecord(ctx->ev_sort, pl.sort_stream));
         HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sort, 0));
@@ -898,7 +893,7 @@ int32_t msm_core(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, const ui
             int32_t r = msm_enqueue(ctx, d_scalars + lo * 32, m, d_pts + lo * (PTS_BYTES / 4), g, dslot(ctx, 0), nullptr, nullptr);
             if (r) return r;
             if ((r = slots_collect(ctx, 1))) return r;
-            if (slot_flags((uint32_t *)hslot(ctx, 0))[0]) { ctx->err = "msm: a scalar has bit 255 set (Scalar invariant #1 violated)"; return -(int32_t)hipErrorInvalidValue; }
+            if (slot_flags((uint32_t *)hslot(ctx, 0))[0]) return bad_arg(ctx, "msm: a scalar has bit 255 set (Scalar invariant #1 violated)");
             R = ge_add(R, msm_horner(hslot(ctx, 0), g));
         }
         if (n == 0) break;
@@ -927,7 +922,7 @@ int32_t msm_merged_build(c25519_ctx *ctx, const uint8_t *d_points, uint64_t ns, 
     if (in_fmt == C25519_FMT_RAW160) HIPCHK(hipMemcpyAsync(raw, d_points, ns * 160, hipMemcpyDeviceToDevice, st));
     else if (in_fmt == C25519_FMT_EDWARDS_Y) HIPCHK(launch_decompress_edwards(d_points, ns, raw, ok, d_badcount, st));
     else if (in_fmt == C25519_FMT_RISTRETTO) HIPCHK(launch_decompress_ristretto(d_points, ns, raw, ok, d_badcount, st));
-    else { ctx->err = "precomp: bad in_fmt"; return -(int32_t)hipErrorInvalidValue; }
+    else return bad_arg(ctx, "precomp: bad in_fmt");
     launch_merged_table(raw, ns, m.c, m.K, (uint8_t *)ctx->tmp_f.p, st);
     HIPCHK(hipGetLastError());
     return prep_points(ctx, (const uint8_t *)ctx->tmp_f.p, (uint64_t)m.K * ns, C25519_FMT_RAW160, d_table, 0, d_badcount + 1);
@@ -947,7 +942,7 @@ int32_t msm_merged_core(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, c
     if (r) return r;
     if ((r = msm_enqueue_acc(ctx, pl, d_table, dslot(ctx, 0), nullptr, nullptr))) return r;
     if ((r = slots_collect(ctx, 1))) return r;
-    if (slot_flags((uint32_t *)hslot(ctx, 0))[0]) { ctx->err = "precomp_msm: internal error (top digit out of range)"; return -(int32_t)hipErrorInvalidValue; }
+    if (slot_flags((uint32_t *)hslot(ctx, 0))[0]) return bad_arg(ctx, "precomp_msm: internal error (top digit out of range)");
     R = host_p40(hslot(ctx, 0));                          // one window at position 0: the column sum IS the result
     return C25519_OK;
 }
@@ -1008,7 +1003,7 @@ int32_t prep_points_on(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n, int
         else if (CH == 8) hipLaunchKernelGGL((k_prep_raw2<8, wpb>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
         else if (CH == 4) hipLaunchKernelGGL((k_prep_raw2<4, wpb>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
         else hipLaunchKernelGGL((k_prep_raw2<16, wpb>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
-    } else { ctx->err = "msm: bad in_fmt"; return -(int32_t)hipErrorInvalidValue; }
+    } else return bad_arg(ctx, "msm: bad in_fmt");
     HIPCHK(hipGetLastError());
     return C25519_OK;
 }
@@ -1133,7 +1128,7 @@ static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_
     if (serial_sort) { HIPCHK(hipEventRecord(ctx->ev_z, ctx->stream)); HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_z, 0)); }
     if (!sorted_first && (r = msm_enqueue_sort(ctx, d_scalars, n, g, d_slot, ctx->aux, pl, nullptr, n_carve, lists_free, sweep_early >= 2 ? parity : -1))) return r;
     // a continuing pass adds onto the bucket sums its predecessor on this stream set left: they must be where it left them
-    if (cont && pl.buckets != ctx->cont_buckets) { ctx->err = "msm: internal error (the workspace of a continuing pass moved its buckets)"; return -(int32_t)hipErrorInvalidValue; }
+    if (cont && pl.buckets != ctx->cont_buckets) return bad_arg(ctx, "msm: internal error (the workspace of a continuing pass moved its buckets)");
     ctx->cont_buckets = pl.buckets;
     if ((r = msm_enqueue_acc(ctx, pl, d_pts, d_slot, ring, wait_acc, cont, reduce, d_bad_sticky))) return r;
     return C25519_OK;
@@ -1148,8 +1143,8 @@ typedef std::function<int32_t(uint64_t lo, uint64_t m, hipEvent_t *ready)> msm_f
 static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, uint32_t *d_record,
                                   const msm_fetch *fetch = nullptr, uint64_t pass_terms = 0) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (in_fmt < 0 || in_fmt > 2) { ctx->err = "msm: bad in_fmt"; return -(int32_t)hipErrorInvalidValue; }
-    if (n >= (1ull << 40)) { ctx->err = "msm: n must be < 2^40"; return -(int32_t)hipErrorInvalidValue; }
+    if (in_fmt < 0 || in_fmt > 2) return bad_arg(ctx, "msm: bad in_fmt");
+    if (n >= (1ull << 40)) return bad_arg(ctx, "msm: n must be < 2^40");
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     if (n == 0) {                                           // the identity: an empty record (records_fold skips it)
         ctx->last_passes.clear();
@@ -1160,7 +1155,7 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
     }
     const uint64_t PT = pass_terms ? pass_terms : MSM_PASS, PTMAX = pass_terms ? pass_terms + pass_terms / 2 : MSM_PASS_MAX;
     const uint64_t passes = n <= PTMAX ? 1 : (n + PT - 1) / PT, per = (n + passes - 1) / passes;
-    const size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32;
+    const size_t psz = point_bytes(in_fmt);
     msm_geom g;
     pass_set ps;
     int32_t r;
@@ -1348,7 +1343,7 @@ EXPORT int32_t c25519_msm_partial_dev(c25519_ctx *ctx, const uint8_t *d_scalars,
     return C25519_OK;
 }
 EXPORT int32_t c25519_msm_vartime_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *out) {
-    if (out_fmt < 0 || out_fmt > 2) { ctx->err = "msm: bad out_fmt"; return -(int32_t)hipErrorInvalidValue; }
+    if (out_fmt < 0 || out_fmt > 2) return bad_arg(ctx, "msm: bad out_fmt");
     ge_p3 R;
     int32_t r = msm_partial_impl(ctx, d_scalars, d_points, n, in_fmt, R);
     if (r != C25519_OK) return r;
@@ -1358,8 +1353,8 @@ EXPORT int32_t c25519_msm_vartime_dev(c25519_ctx *ctx, const uint8_t *d_scalars,
 }
 EXPORT int32_t c25519_msm_vartime(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, int out_fmt, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (out_fmt < 0 || out_fmt > 2 || in_fmt < 0 || in_fmt > 2) { ctx->err = "msm: bad format"; return -(int32_t)hipErrorInvalidValue; }
-    const size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32;
+    if (out_fmt < 0 || out_fmt > 2 || in_fmt < 0 || in_fmt > 2) return bad_arg(ctx, "msm: bad format");
+    const size_t psz = point_bytes(in_fmt);
     int32_t r;
     ctx->host_us[0] = wall_us();
     if (n <= msm_small_max()) {

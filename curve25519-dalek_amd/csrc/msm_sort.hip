@@ -18,14 +18,9 @@
 #include "msm_internal.h"
 #include "msm_sort.h"
 #include "ffi.h"
+#include "capi_util.h"
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
 
 
 namespace c25519 {
@@ -420,7 +415,7 @@ int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_s
     const uint64_t nc = n_carve > n ? n_carve : n;
     // The chunk-local sort serves every plain MSM pass: its per-bin counting sort scans 2^bps_log2 >= 64 buckets per wave, i.e. windows of
     // c >= 7 bits (n >= 2048 terms; inputs below 4096 terms never get here, msm_small_enqueue), and its entries keep a 23-bit term index.
-    if (!md && (g.half < 64 || n > (1ull << (part_entry_shift(g) - 1)))) { ctx->err = "msm: internal error (a pass outside the range of the chunk-local sort)"; return -(int32_t)hipErrorInvalidValue; }
+    if (!md && (g.half < 64 || n > (1ull << (part_entry_shift(g) - 1)))) return bad_arg(ctx, "msm: internal error (a pass outside the range of the chunk-local sort)");
     // which sort: the digit-matrix sort for the merged layout and for plain passes below 2^16 terms (the chunk-local partition wants hundreds of
     // chunks: msm_sort_matrix.hip has the numbers); C25519_SORT_CHUNK_LOCAL_MIN lowers the boundary (tests run the chunk-local sort from 2 048 terms)
     static const uint64_t chunk_local_min = (uint64_t)C25519_KNOB("SORT_CHUNK_LOCAL_MIN", 1 << 16);
@@ -474,7 +469,7 @@ int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_s
     const int ngr = g.ngroups > 1 ? g.ngroups : 1;
     uint32_t *ord_cursor = flags + 64 + 256 * ngr, *bad_ws = flags + 64 + 512 * ngr;
     const int ZERO_WORDS = 64 + 512 * ngr;
-    if (ngr > 1 && (matrix || g.half < 1024)) { ctx->err = "msm: internal error (window groups outside the chunk-local sort)"; return -(int32_t)hipErrorInvalidValue; }
+    if (ngr > 1 && (matrix || g.half < 1024)) return bad_arg(ctx, "msm: internal error (window groups outside the chunk-local sort)");
     pl.g = g; pl.n = n; pl.nb = nb; pl.nseg = nseg; pl.max_items = max_items; pl.max_long = max_long;
     pl.base = base; pl.sorted = sorted; pl.buckets = buckets; pl.perm = perm; pl.SW = (uint32_t *)(ws + oSW); pl.counters = flags + 8; pl.bad_ws = bad_ws;
     pl.items = (long_item *)(ws + oLI); pl.lgids = (uint32_t *)(ws + oLG); pl.lfirst = (uint32_t *)(ws + oLF); pl.segs = (uint32_t *)(ws + oLS);

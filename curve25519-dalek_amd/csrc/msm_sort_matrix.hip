@@ -22,14 +22,9 @@
 #include "msm_internal.h"
 #include "msm_sort.h"
 #include "ffi.h"
+#include "capi_util.h"
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
 
 
 namespace c25519 {

@@ -26,14 +26,9 @@
 #include "kernels.h"
 #include "ctx.h"
 #include "ffi.h"
+#include "capi_util.h"
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
 
 namespace c25519 {
 
@@ -280,12 +275,10 @@ __global__ void __launch_bounds__(256) k_place_R(const uint8_t *__restrict__ Ren
 
 }  // namespace c25519
 
-static inline unsigned dup(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
-
 // ---- variable base ------------------------------------------------------------------------------------
 // ct: the scalars are secret (constant-address table scan); false for public scalars (per-signature verification)
 static int32_t var_base_launch(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, bool negate, bool ct, uint32_t *out40, uint8_t *d_ok) {
-    const unsigned grid = dup(n, 256);
+    const unsigned grid = div_up(n, 256);
     const uint64_t stride = (uint64_t)grid * 256;
     int32_t r = ctx_reserve(ctx, ctx->tmp_d, stride * 9 * 160);
     if (r) return r;
@@ -298,7 +291,7 @@ static int32_t var_base_launch(c25519_ctx *ctx, const uint8_t *d_scalars, const 
     } else if (in_fmt == C25519_FMT_RAW160) {
         if (negate) { if (ct) VB(2, true, true); else VB(2, true, false); }
         else { if (ct) VB(2, false, true); else VB(2, false, false); }
-    } else { ctx->err = "mul_batch: in_fmt must be 0 or 2"; return -(int32_t)hipErrorInvalidValue; }
+    } else return bad_arg(ctx, "mul_batch: in_fmt must be 0 or 2");
 #undef VB
     HIPCHK(hipGetLastError());
     if (ct) HIPCHK(hipMemsetAsync(tab, 0, stride * 9 * 160, st));     // the per-lane tables are multiples of a possibly secret point path: wipe
@@ -307,7 +300,7 @@ static int32_t var_base_launch(c25519_ctx *ctx, const uint8_t *d_scalars, const 
 
 int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok, bool ct) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (out_fmt != C25519_FMT_EDWARDS_Y && out_fmt != C25519_FMT_RAW160) { ctx->err = "mul_batch: out_fmt must be 0 or 2"; return -(int32_t)hipErrorInvalidValue; }
+    if (!ed_fmt_ok(out_fmt)) return bad_arg(ctx, "mul_batch: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_e, n * 160 + n + 256))) return r;
@@ -319,12 +312,12 @@ int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
     if ((r = var_base_launch(ctx, d_scalars, d_points, n, in_fmt, false, ct, p40, okbuf))) return r;
     HIPCHK(hipEventRecord(ring[1], ctx->stream));
     if (out_fmt == C25519_FMT_RAW160) {
-        hipLaunchKernelGGL(k_p40_to_raw, dim3(dup(n, 256)), dim3(256), 0, ctx->stream, p40, (const uint32_t *)nullptr, n, d_out);
+        hipLaunchKernelGGL(k_p40_to_raw, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, p40, (const uint32_t *)nullptr, n, d_out);
     } else {
         if ((r = ctx_reserve(ctx, ctx->scratch, n * 128)) || (r = ctx_reserve(ctx, ctx->prefix, n * 48))) return r;
         stream_wipe wipe(ctx->stream);                    // (declared before the launches: also wiped if one of them fails)
         if (ct) { wipe.add(ctx->scratch.p, n * 128); wipe.add(ctx->prefix.p, n * 48); }
-        hipLaunchKernelGGL(k_p40_add_to_p32, dim3(dup(n, 256)), dim3(256), 0, ctx->stream, p40, (const uint32_t *)nullptr, n, (uint32_t *)ctx->scratch.p);
+        hipLaunchKernelGGL(k_p40_add_to_p32, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, p40, (const uint32_t *)nullptr, n, (uint32_t *)ctx->scratch.p);
         HIPCHK(launch_compress_p32((const uint32_t *)ctx->scratch.p, (uint32_t *)ctx->prefix.p, n, d_out, ctx->stream));
     }
     HIPCHK(hipGetLastError());
@@ -370,54 +363,40 @@ __global__ void __launch_bounds__(256) k_flag_identity_enc(const uint8_t *__rest
 }  // namespace c25519
 EXPORT int32_t c25519_point_order_checks_batch_dev(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n, int in_fmt, int which, uint8_t *d_flags) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (in_fmt != C25519_FMT_EDWARDS_Y && in_fmt != C25519_FMT_RAW160) { ctx->err = "point_order_checks: in_fmt must be 0 or 2"; return -(int32_t)hipErrorInvalidValue; }
-    if (!(which & (C25519_POINT_SMALL_ORDER | C25519_POINT_TORSION_FREE))) { ctx->err = "point_order_checks: nothing to check"; return -(int32_t)hipErrorInvalidValue; }
+    if (!ed_fmt_ok(in_fmt)) return bad_arg(ctx, "point_order_checks: in_fmt must be 0 or 2");
+    if (!(which & (C25519_POINT_SMALL_ORDER | C25519_POINT_TORSION_FREE))) return bad_arg(ctx, "point_order_checks: nothing to check");
     if (n == 0) return C25519_OK;
     const bool small = (which & C25519_POINT_SMALL_ORDER) != 0;
     if (small) {
-        if (in_fmt == C25519_FMT_EDWARDS_Y) hipLaunchKernelGGL(k_small_order<0>, dim3(dup(n, 256)), dim3(256), 0, ctx->stream, d_points, n, d_flags);
-        else hipLaunchKernelGGL(k_small_order<2>, dim3(dup(n, 256)), dim3(256), 0, ctx->stream, d_points, n, d_flags);
+        if (in_fmt == C25519_FMT_EDWARDS_Y) hipLaunchKernelGGL(k_small_order<0>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_points, n, d_flags);
+        else hipLaunchKernelGGL(k_small_order<2>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_points, n, d_flags);
         HIPCHK(hipGetLastError());
     }
     if (which & C25519_POINT_TORSION_FREE) {
         int32_t r;
         if ((r = ctx_reserve(ctx, ctx->tmp_c2, n * 65 + 64))) return r;
         uint8_t *l = (uint8_t *)ctx->tmp_c2.p, *enc = l + n * 32, *ok = enc + n * 32;
-        hipLaunchKernelGGL(k_fill_order, dim3(dup(n, 256)), dim3(256), 0, ctx->stream, n, l);
+        hipLaunchKernelGGL(k_fill_order, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, n, l);
         if ((r = mul_batch_impl(ctx, l, d_points, n, in_fmt, C25519_FMT_EDWARDS_Y, enc, ok, false))) return r;     // public points, public scalar: the fast tables
-        hipLaunchKernelGGL(k_flag_identity_enc, dim3(dup(n, 256)), dim3(256), 0, ctx->stream, enc, ok, n, d_flags, small ? 0 : 1);
+        hipLaunchKernelGGL(k_flag_identity_enc, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, enc, ok, n, d_flags, small ? 0 : 1);
         HIPCHK(hipGetLastError());
     }
     return C25519_OK;
 }
 EXPORT int32_t c25519_point_order_checks_batch(c25519_ctx *ctx, const uint8_t *points, uint64_t n, int in_fmt, int which, uint8_t *flags) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (in_fmt != C25519_FMT_EDWARDS_Y && in_fmt != C25519_FMT_RAW160) { ctx->err = "point_order_checks: in_fmt must be 0 or 2"; return -(int32_t)hipErrorInvalidValue; }
-    const size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32;
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * psz + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n + 16))) return r;
-    uint8_t *dp = (uint8_t *)ctx->tmp_a.p, *dfl = (uint8_t *)ctx->tmp_b.p;
-    const ffi_in in = {points, dp, psz};
-    const ffi_out o = {flags, dfl, 1};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 16), &in, 1, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return c25519_point_order_checks_batch_dev(ctx, dp + lo * psz, m, in_fmt, which, dfl + lo);
-    });
+    if (!ed_fmt_ok(in_fmt)) return bad_arg(ctx, "point_order_checks: in_fmt must be 0 or 2");
+    return ffi_twin(ctx, n, 1u << 16, {{points, point_bytes(in_fmt), FFI_TMP_A, 16}}, {{flags, 1, FFI_TMP_B, 16}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_point_order_checks_batch_dev(ctx, d_in[0], m, in_fmt, which, d_out[0]); });
 }
 static int32_t mul_batch_host(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, int out_fmt, uint8_t *out, uint8_t *ok, bool clamp) {
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32, osz = out_fmt == C25519_FMT_RAW160 ? 160 : 32;
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * psz + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * osz + n + 16))) return r;
-    uint8_t *ds = (uint8_t *)ctx->tmp_a.p, *dp = (uint8_t *)ctx->tmp_b.p, *dout = (uint8_t *)ctx->tmp_c.p, *dok = dout + n * osz;
-    const bool secret = ctx_secret_default(ctx);
-    stream_wipe wipe(ctx->stream);
-    if (secret) { wipe.add(ds, n * 32); wipe.add(dout, n * osz); }        // staged secret scalars and the products (e.g. shared secrets)
-    const ffi_in in[2] = {{scalars, ds, 32}, {points, dp, psz}};
-    const ffi_out o[2] = {{out, dout, osz}, {ok, dok, 1}};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 16), in, 2, o, 2, [&](uint64_t lo, uint64_t m) -> int32_t {
-        if (clamp) HIPCHK(launch_clamp(ds + lo * 32, m, ds + lo * 32, ctx->stream));
-        return mul_batch_impl(ctx, ds + lo * 32, dp + lo * psz, m, in_fmt, out_fmt, dout + lo * osz, dok + lo, secret);
-    });
+    const bool secret = ctx_secret_default(ctx);         // wipes the staged secret scalars and the products (e.g. shared secrets)
+    return ffi_twin(ctx, n, 1u << 16, {{scalars, 32, FFI_TMP_A, 16, secret}, {points, point_bytes(in_fmt), FFI_TMP_B, 16}},
+                    {{out, point_bytes(out_fmt), FFI_TMP_C, 16, secret}, {ok, 1, FFI_TMP_C}}, [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) -> int32_t {
+                        if (clamp) HIPCHK(launch_clamp(d_in[0], m, d_in[0], ctx->stream));
+                        return mul_batch_impl(ctx, d_in[0], d_in[1], m, in_fmt, out_fmt, d_out[0], d_out[1], secret);
+                    });
 }
 EXPORT int32_t c25519_mul_batch(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, int out_fmt, uint8_t *out, uint8_t *ok) {
     return mul_batch_host(ctx, scalars, points, n, in_fmt, out_fmt, out, ok, false);
@@ -440,7 +419,7 @@ EXPORT int32_t c25519_mul_clamped_batch(c25519_ctx *ctx, const uint8_t *bytes, c
 EXPORT int32_t c25519_double_base_batch_dev(c25519_ctx *ctx, const uint8_t *d_a, const uint8_t *d_A, const uint8_t *d_b, uint64_t n, int in_fmt, int out_fmt,
                                             uint8_t *d_out, uint8_t *d_ok) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (out_fmt != C25519_FMT_EDWARDS_Y && out_fmt != C25519_FMT_RAW160) { ctx->err = "double_base: out_fmt must be 0 or 2"; return -(int32_t)hipErrorInvalidValue; }
+    if (!ed_fmt_ok(out_fmt)) return bad_arg(ctx, "double_base: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_e, 2 * n * 160 + n + 256))) return r;
@@ -454,10 +433,10 @@ EXPORT int32_t c25519_double_base_batch_dev(c25519_ctx *ctx, const uint8_t *d_a,
     HIPCHK(hipEventRecord(ring[1], st));
     HIPCHK(launch_mul_base_p40(ctx->w, d_b, n, ctx->d_table, Q40, ctx->num_cus, st));                 // b * B (public)
     if (out_fmt == C25519_FMT_RAW160) {
-        hipLaunchKernelGGL(k_p40_to_raw, dim3(dup(n, 256)), dim3(256), 0, st, P40, Q40, n, d_out);
+        hipLaunchKernelGGL(k_p40_to_raw, dim3(div_up(n, 256)), dim3(256), 0, st, P40, Q40, n, d_out);
     } else {
         if ((r = ctx_reserve(ctx, ctx->scratch, n * 128)) || (r = ctx_reserve(ctx, ctx->prefix, n * 48))) return r;
-        hipLaunchKernelGGL(k_p40_add_to_p32, dim3(dup(n, 256)), dim3(256), 0, st, P40, Q40, n, (uint32_t *)ctx->scratch.p);
+        hipLaunchKernelGGL(k_p40_add_to_p32, dim3(div_up(n, 256)), dim3(256), 0, st, P40, Q40, n, (uint32_t *)ctx->scratch.p);
         HIPCHK(launch_compress_p32((const uint32_t *)ctx->scratch.p, (uint32_t *)ctx->prefix.p, n, d_out, st));
     }
     HIPCHK(hipGetLastError());
@@ -468,15 +447,10 @@ EXPORT int32_t c25519_double_base_batch_dev(c25519_ctx *ctx, const uint8_t *d_a,
 EXPORT int32_t c25519_double_base_batch(c25519_ctx *ctx, const uint8_t *a, const uint8_t *A, const uint8_t *b, uint64_t n, int in_fmt, int out_fmt,
                                         uint8_t *out, uint8_t *ok) {
     HIPCHK(hipSetDevice(ctx->device));
-    const size_t psz = in_fmt == C25519_FMT_RAW160 ? 160 : 32, osz = out_fmt == C25519_FMT_RAW160 ? 160 : 32;
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, 2 * n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * psz + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * osz + n + 16))) return r;
-    uint8_t *da = (uint8_t *)ctx->tmp_a.p, *db = da + n * 32, *dA = (uint8_t *)ctx->tmp_b.p, *dout = (uint8_t *)ctx->tmp_c.p, *dok = dout + n * osz;
-    const ffi_in in[3] = {{a, da, 32}, {b, db, 32}, {A, dA, psz}};
-    const ffi_out o[2] = {{out, dout, osz}, {ok, dok, 1}};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 16), in, 3, o, 2, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return c25519_double_base_batch_dev(ctx, da + lo * 32, dA + lo * psz, db + lo * 32, m, in_fmt, out_fmt, dout + lo * osz, dok + lo);
-    });
+    return ffi_twin(ctx, n, 1u << 16, {{a, 32, FFI_TMP_A, 16}, {b, 32, FFI_TMP_A}, {A, point_bytes(in_fmt), FFI_TMP_B, 16}},
+                    {{out, point_bytes(out_fmt), FFI_TMP_C, 16}, {ok, 1, FFI_TMP_C}}, [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) {
+                        return c25519_double_base_batch_dev(ctx, d_in[0], d_in[2], d_in[1], m, in_fmt, out_fmt, d_out[0], d_out[1]);
+                    });
 }
 
 // ---- per-signature verify ---------------------------------------------------------------------------------
@@ -484,7 +458,7 @@ EXPORT int32_t c25519_double_base_batch(c25519_ctx *ctx, const uint8_t *a, const
 // copy lives in the context until the next call, so the asynchronous upload never reads a dead frame
 static int32_t dom2_upload(c25519_ctx *ctx, const uint8_t *context, uint32_t context_len, const uint8_t **d_dom, uint32_t *dom_len) {
     if (context_len > 255) { ctx->err = "prehashed: the context must not be longer than 255 octets"; return C25519_PREHASHED_CONTEXT_LENGTH; }    // signing.rs:931-933
-    if (context_len && !context) { ctx->err = "prehashed: null context"; return -(int32_t)hipErrorInvalidValue; }
+    if (context_len && !context) return bad_arg(ctx, "prehashed: null context");
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->dom, 512))) return r;
     ctx->h_dom.assign(34 + context_len, 0);
@@ -514,15 +488,15 @@ static int32_t verify_each_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const ui
     HIPCHK(hipMemsetAsync(ctx->d_flag, 0, 16, st));
     if (d_dom) HIPCHK(launch_hram_dom(d_dom, dom_len, d_msgs, nullptr, n * 64, 64, d_sigs, d_pks, n, hram, (uint32_t *)ctx->d_flag, st));
     else HIPCHK(launch_hram(d_msgs, d_msg_off, msgs_len, d_sigs, d_pks, n, hram, (uint32_t *)ctx->d_flag, st));
-    hipLaunchKernelGGL(k_hram_reduce, dim3(dup(n, 256)), dim3(256), 0, st, hram, d_sigs, n, kscal, sscal, s_ok);
+    hipLaunchKernelGGL(k_hram_reduce, dim3(div_up(n, 256)), dim3(256), 0, st, hram, d_sigs, n, kscal, sscal, s_ok);
     HIPCHK(hipEventRecord(ring[0], st));
     if ((r = var_base_launch(ctx, kscal, d_pks, n, C25519_FMT_EDWARDS_Y, true, false, P40, a_ok))) return r;    // [k](-A), k public
     HIPCHK(hipEventRecord(ring[1], st));
     HIPCHK(launch_mul_base_p40(ctx->w, sscal, n, ctx->d_table, Q40, ctx->num_cus, st));                      // [s]B
-    hipLaunchKernelGGL(k_p40_add_to_p32, dim3(dup(n, 256)), dim3(256), 0, st, P40, Q40, n, (uint32_t *)ctx->scratch.p);
+    hipLaunchKernelGGL(k_p40_add_to_p32, dim3(div_up(n, 256)), dim3(256), 0, st, P40, Q40, n, (uint32_t *)ctx->scratch.p);
     HIPCHK(launch_compress_p32((const uint32_t *)ctx->scratch.p, (uint32_t *)ctx->prefix.p, n, rcheck, st));
-    if (strict) hipLaunchKernelGGL(k_strict_checks, dim3(dup(n, 256)), dim3(256), 0, st, d_sigs, d_pks, n, sbad);
-    hipLaunchKernelGGL(k_verdict, dim3(dup(n, 256)), dim3(256), 0, st, d_sigs, rcheck, a_ok, s_ok, strict ? sbad : (const uint8_t *)nullptr, n, d_status);
+    if (strict) hipLaunchKernelGGL(k_strict_checks, dim3(div_up(n, 256)), dim3(256), 0, st, d_sigs, d_pks, n, sbad);
+    hipLaunchKernelGGL(k_verdict, dim3(div_up(n, 256)), dim3(256), 0, st, d_sigs, rcheck, a_ok, s_ok, strict ? sbad : (const uint8_t *)nullptr, n, d_status);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ring[2], st));
     HIPCHK(hipEventRecord(ctx->ev1, st));
@@ -548,36 +522,25 @@ EXPORT int32_t ed25519_verify_each_prehashed(c25519_ctx *ctx, const uint8_t *pre
     HIPCHK(hipSetDevice(ctx->device));
     if (context_len > 255) { ctx->err = "prehashed: the context must not be longer than 255 octets"; return C25519_PREHASHED_CONTEXT_LENGTH; }
     if (n == 0) return C25519_OK;
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 64 + 64)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 64 + n * 32 + n + 64))) return r;
-    uint8_t *dph = (uint8_t *)ctx->tmp_a.p, *dsig = (uint8_t *)ctx->tmp_c.p, *dpk = dsig + n * 64, *dst = dpk + n * 32;
-    const ffi_in in[3] = {{prehashes, dph, 64}, {sigs, dsig, 64}, {pks, dpk, 32}};
-    const ffi_out o = {status, dst, 1};
-    return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 16), in, 3, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return ed25519_verify_each_prehashed_dev(ctx, dph + lo * 64, context, context_len, dsig + lo * 64, dpk + lo * 32, m, strict, dst + lo);
-    });
+    return ffi_twin(ctx, n, 1u << 16, {{prehashes, 64, FFI_TMP_A, 64}, {sigs, 64, FFI_TMP_C, 64}, {pks, 32, FFI_TMP_C}}, {{status, 1, FFI_TMP_C}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) {
+                        return ed25519_verify_each_prehashed_dev(ctx, d_in[0], context, context_len, d_in[1], d_in[2], m, strict, d_out[0]);
+                    });
 }
 EXPORT int32_t ed25519_verify_each(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *sigs, const uint8_t *pks,
                                    uint64_t n, int strict, uint8_t *status) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
-    for (uint64_t i = 0; i < n; i++) if (msg_off[i] > msg_off[i + 1]) { ctx->err = "verify_each: msg_off is not monotone"; return -(int32_t)hipErrorInvalidValue; }
-    const uint64_t mlen = msg_off[n];
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, mlen + 64)) || (r = ctx_reserve(ctx, ctx->tmp_b, (n + 1) * 8)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 64 + n * 32 + n + 64))) return r;
-    uint8_t *dmsg = (uint8_t *)ctx->tmp_a.p, *dsig = (uint8_t *)ctx->tmp_c.p, *dpk = dsig + n * 64, *dst = dpk + n * 32;
-    uint64_t *doff = (uint64_t *)ctx->tmp_b.p;
-    // the message blob and the offsets go up whole (the kernels index the blob through the offsets); signatures and keys in chunks
-    if ((r = ffi_begin(ctx))) return r;
-    ffi_guard guard(ctx);                                 // an early exit below still drains the copy stream
-    if (mlen) HIPCHK(hipMemcpyAsync(dmsg, msgs, mlen, hipMemcpyHostToDevice, ctx->s_h2d));
-    HIPCHK(hipMemcpyAsync(doff, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_h2d));
+    // the message blob and the offsets go up whole; signatures and keys in chunks
+    ffi_msgs mm;
+    int32_t r = ffi_upload_msgs(ctx, msgs, msg_off, n, "verify_each: msg_off is not monotone", n * 64 + n * 32 + n + 64, mm);
+    if (r) return r;
+    uint8_t *dsig = (uint8_t *)ctx->tmp_c.p, *dpk = dsig + n * 64, *dst = dpk + n * 32;
     const ffi_in in[2] = {{sigs, dsig, 64}, {pks, dpk, 32}};
     const ffi_out o = {status, dst, 1};
-    guard.dismiss();                                      // ffi_pipeline calls ffi_end on every path
     return ffi_pipeline(ctx, n, ffi_chunk_units(n, 1u << 16), in, 2, &o, 1, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return ed25519_verify_each_dev(ctx, dmsg, doff + lo, mlen, dsig + lo * 64, dpk + lo * 32, m, strict, dst + lo);
-    }, true, mlen + (n + 1) * 8);
+        return ed25519_verify_each_dev(ctx, mm.d_msgs, mm.d_off + lo, mm.mlen, dsig + lo * 64, dpk + lo * 32, m, strict, dst + lo);
+    }, true, mm.up_bytes);
 }
 
 // ---- key generation / signing -------------------------------------------------------------------------------
@@ -587,7 +550,7 @@ EXPORT int32_t ed25519_keygen_batch_dev(c25519_ctx *ctx, const uint8_t *d_seeds,
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_f, n * 64 + 256))) return r;
     uint8_t *a = (uint8_t *)ctx->tmp_f.p, *prefix = a + n * 32;
-    hipLaunchKernelGGL(k_expand_seed, dim3(dup(n, 256)), dim3(256), 0, ctx->stream, d_seeds, n, a, prefix);
+    hipLaunchKernelGGL(k_expand_seed, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, d_seeds, n, a, prefix);
     r = mul_base_impl(ctx, a, n, C25519_FMT_EDWARDS_Y, d_pks, ctx_secret_default(ctx));       // secret scalar: constant-time tables
     hipError_t e = hipMemsetAsync(a, 0, n * 64, ctx->stream);   // wipe the expanded secrets, on every path
     if (r) return r;
@@ -605,17 +568,17 @@ static int32_t sign_body(c25519_ctx *ctx, const uint8_t *d_seeds, const uint8_t 
     // A = a*B and R = r*B (the nonce is as secret as the key) in ONE fixed-base launch over the 2n scalars a || r: the nonce
     // r = H(prefix || M) does not depend on A, and a batch of 2^16 signatures is two launches' worth of latency otherwise
     // (2 x (0.21 + 0.10) ms of a 0.83 ms call, profiles/r03_sign_keygen_2p16.txt).  rscal = a + 32 n, Renc = AR + 32 n.
-    hipLaunchKernelGGL(k_expand_seed, dim3(dup(n, 256)), dim3(256), 0, st, d_seeds, n, a, prefix);
-    if (d_dom) hipLaunchKernelGGL(k_sign_nonce_dom, dim3(dup(n, 256)), dim3(256), 0, st, d_dom, dom_len, prefix, d_msgs, n, rscal);
-    else hipLaunchKernelGGL(k_sign_nonce, dim3(dup(n, 256)), dim3(256), 0, st, prefix, d_msgs, d_msg_off, msgs_len, n, rscal);
+    hipLaunchKernelGGL(k_expand_seed, dim3(div_up(n, 256)), dim3(256), 0, st, d_seeds, n, a, prefix);
+    if (d_dom) hipLaunchKernelGGL(k_sign_nonce_dom, dim3(div_up(n, 256)), dim3(256), 0, st, d_dom, dom_len, prefix, d_msgs, n, rscal);
+    else hipLaunchKernelGGL(k_sign_nonce, dim3(div_up(n, 256)), dim3(256), 0, st, prefix, d_msgs, d_msg_off, msgs_len, n, rscal);
     uint8_t *AR = Renc - n * 32;
     if ((r = mul_base_impl(ctx, a, 2 * n, C25519_FMT_EDWARDS_Y, AR, secret))) return r;
     HIPCHK(hipMemcpyAsync(d_pks, AR, n * 32, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_place_R, dim3(dup(n, 256)), dim3(256), 0, st, Renc, n, d_sigs);
+    hipLaunchKernelGGL(k_place_R, dim3(div_up(n, 256)), dim3(256), 0, st, Renc, n, d_sigs);
     HIPCHK(hipMemsetAsync(ctx->d_flag, 0, 16, st));
     if (d_dom) HIPCHK(launch_hram_dom(d_dom, dom_len, d_msgs, nullptr, n * 64, 64, d_sigs, d_pks, n, hram, (uint32_t *)ctx->d_flag, st));      // k = H(dom2||R||A||PH(M))
     else HIPCHK(launch_hram(d_msgs, d_msg_off, msgs_len, d_sigs, d_pks, n, hram, (uint32_t *)ctx->d_flag, st));          // k = H(R||A||M)
-    hipLaunchKernelGGL(k_sign_finish, dim3(dup(n, 256)), dim3(256), 0, st, hram, a, rscal, Renc, n, d_sigs);
+    hipLaunchKernelGGL(k_sign_finish, dim3(div_up(n, 256)), dim3(256), 0, st, hram, a, rscal, Renc, n, d_sigs);
     HIPCHK(hipGetLastError());
     return C25519_OK;
 }
@@ -636,7 +599,7 @@ static int32_t sign_batch_dev_impl(c25519_ctx *ctx, const uint8_t *d_seeds, cons
     uint32_t fl[4] = {0, 0, 0, 0};                              // bad message offsets (k_hram) -> error, like verify_batch
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpy(fl, ctx->d_flag, 16, hipMemcpyDeviceToHost));      // (blocking: no copy is ever pending into this frame)
-    if (fl[1]) { ctx->err = "sign_batch: msg_off is not monotone or runs past msgs_len"; return -(int32_t)hipErrorInvalidValue; }
+    if (fl[1]) return bad_arg(ctx, "sign_batch: msg_off is not monotone or runs past msgs_len");
     return C25519_OK;
 }
 EXPORT int32_t ed25519_sign_batch_dev(c25519_ctx *ctx, const uint8_t *d_seeds, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len,
@@ -659,38 +622,26 @@ EXPORT int32_t ed25519_sign_batch_prehashed(c25519_ctx *ctx, const uint8_t *seed
     HIPCHK(hipSetDevice(ctx->device));
     if (context_len > 255) { ctx->err = "prehashed: the context must not be longer than 255 octets"; return C25519_PREHASHED_CONTEXT_LENGTH; }
     if (n == 0) return C25519_OK;
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 64 + 64)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 128 + 64))) return r;
-    uint8_t *dph = (uint8_t *)ctx->tmp_a.p, *dseed = (uint8_t *)ctx->tmp_c.p, *dpk = dseed + n * 32, *dsig = dpk + n * 32;
-    stream_wipe wipe(ctx->stream);
-    wipe.add(dseed, n * 32);                              // the staged secret keys, on every path
-    const ffi_in in[2] = {{seeds, dseed, 32}, {prehashes, dph, 64}};
-    const ffi_out o[2] = {{pks, dpk, 32}, {sigs, dsig, 64}};
-    // one chunk: the signing body reads its error flag back (a synchronisation per call)
-    return ffi_pipeline(ctx, n, n, in, 2, o, 2, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return ed25519_sign_batch_prehashed_dev(ctx, dseed + lo * 32, dph + lo * 64, context, context_len, m, dpk + lo * 32, dsig + lo * 64);
-    });
+    // one chunk: the signing body reads its error flag back (a synchronisation per call); the staged secret keys are wiped
+    return ffi_twin(ctx, n, n, {{seeds, 32, FFI_TMP_C, 64, true}, {prehashes, 64, FFI_TMP_A, 64}}, {{pks, 32, FFI_TMP_C}, {sigs, 64, FFI_TMP_C}},
+                    [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) {
+                        return ed25519_sign_batch_prehashed_dev(ctx, d_in[0], d_in[1], context, context_len, m, d_out[0], d_out[1]);
+                    });
 }
 EXPORT int32_t ed25519_sign_batch(c25519_ctx *ctx, const uint8_t *seeds, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, uint8_t *pks, uint8_t *sigs) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
-    for (uint64_t i = 0; i < n; i++) if (msg_off[i] > msg_off[i + 1]) { ctx->err = "sign_batch: msg_off is not monotone"; return -(int32_t)hipErrorInvalidValue; }
-    const uint64_t mlen = msg_off[n];
-    int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, mlen + 64)) || (r = ctx_reserve(ctx, ctx->tmp_b, (n + 1) * 8)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 128 + 64))) return r;
-    uint8_t *dmsg = (uint8_t *)ctx->tmp_a.p, *dseed = (uint8_t *)ctx->tmp_c.p, *dpk = dseed + n * 32, *dsig = dpk + n * 32;
-    uint64_t *doff = (uint64_t *)ctx->tmp_b.p;
+    // the staged secret keys (the first n x 32 bytes of tmp_c) are wiped on every path; the upload's guard drains the copy stream
+    // before `wipe` is destroyed, so the memset follows completed copies
     stream_wipe wipe(ctx->stream);
-    wipe.add(dseed, n * 32);                              // the staged secret keys, on every path
-    if ((r = ffi_begin(ctx))) return r;
-    ffi_guard guard(ctx);                                 // destroyed before `wipe`: the memset of the staged secrets follows completed copies
-    if (mlen) HIPCHK(hipMemcpyAsync(dmsg, msgs, mlen, hipMemcpyHostToDevice, ctx->s_h2d));
-    HIPCHK(hipMemcpyAsync(doff, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, ctx->s_h2d));
+    ffi_msgs mm;
+    int32_t r = ffi_upload_msgs(ctx, msgs, msg_off, n, "sign_batch: msg_off is not monotone", n * 128 + 64, mm, &wipe, n * 32);
+    if (r) return r;
+    uint8_t *dseed = (uint8_t *)ctx->tmp_c.p, *dpk = dseed + n * 32, *dsig = dpk + n * 32;
     const ffi_in in = {seeds, dseed, 32};
     const ffi_out o[2] = {{pks, dpk, 32}, {sigs, dsig, 64}};
-    guard.dismiss();
     // one chunk: ed25519_sign_batch_dev reads its error flag back (a synchronisation per call)
     return ffi_pipeline(ctx, n, n, &in, 1, o, 2, [&](uint64_t lo, uint64_t m) -> int32_t {
-        return ed25519_sign_batch_dev(ctx, dseed + lo * 32, dmsg, doff + lo, mlen, m, dpk + lo * 32, dsig + lo * 64);
-    }, true, mlen + (n + 1) * 8);
+        return ed25519_sign_batch_dev(ctx, dseed + lo * 32, mm.d_msgs, mm.d_off + lo, mm.mlen, m, dpk + lo * 32, dsig + lo * 64);
+    }, true, mm.up_bytes);
 }

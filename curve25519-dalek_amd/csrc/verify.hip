@@ -20,12 +20,6 @@
 #include "ffi.h"
 
 using namespace c25519;
-#define EXPORT extern "C" __attribute__((visibility("default")))
-#define HIPCHK(call)                                                \
-    do {                                                            \
-        hipError_t _e = (call);                                     \
-        if (_e != hipSuccess) return c25519_fail(ctx, _e, #call);   \
-    } while (0)
 
 namespace c25519 {
 
@@ -322,6 +316,7 @@ void launch_apply_sign(uint32_t *pts, uint64_t dst0, const uint8_t *z16, uint64_
 
 // ---- verify_batch ---------------------------------------------------------------------------------------
 #include "transcript_host.h"
+#include "capi_util.h"
 
 // states of the z tree: iv[l] = the BLAKE2b-256 state after the one-block tag of level l (see k_ztree_first)
 static void ztree_make_ivs(uint64_t n, ztree_ivs &ivs) {
@@ -626,7 +621,7 @@ static int32_t verify_record_verdict(c25519_ctx *ctx, const ge_p3 &R, const uint
 static int32_t verify_record_enqueue(c25519_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points, const uint8_t *d_hram, const uint8_t *d_z16,
                                      uint64_t n, uint32_t *d_record, const verify_pre *pre = nullptr) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (n >= (1ull << 40)) { ctx->err = "verify_batch: n too large"; return -(int32_t)hipErrorInvalidValue; }
+    if (n >= (1ull << 40)) return bad_arg(ctx, "verify_batch: n too large");
     const uint32_t *d_pre = (const uint32_t *)(d_hram + n * 64);
     if (n == 0) { ctx->last_passes.clear(); slot_init(d_record, 0, d_pre, ctx->stream, 0); HIPCHK(hipGetLastError()); return C25519_OK; }
     const uint64_t passes = n <= VERIFY_PASS_MAX ? 1 : (n + VERIFY_PASS - 1) / VERIFY_PASS, per = (n + passes - 1) / passes;
@@ -694,8 +689,8 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
                                  const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points, uint64_t n, uint32_t z_mode, const verify_fetch *fetch) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;                      // batch.rs: 1-term MSM 0*B = identity
-    if (n >= (1ull << 40)) { ctx->err = "verify_batch: n too large"; return -(int32_t)hipErrorInvalidValue; }
-    if (z_mode > 1) { ctx->err = "verify_batch: bad z_mode"; return -(int32_t)hipErrorInvalidValue; }
+    if (n >= (1ull << 40)) return bad_arg(ctx, "verify_batch: n too large");
+    if (z_mode > 1) return bad_arg(ctx, "verify_batch: bad z_mode");
     if (!fetch) ctx->host_us[0] = ctx->host_us[1] = wall_us();      // (c25519_last_call_host_us: entered; the collect functions stamp "enqueued" and "results on the host")
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     int32_t r;
@@ -805,8 +800,8 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
     }
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     if (!fetch) ctx->host_us[4] = wall_us();
-    if (bad_off) { ctx->err = "verify_batch: msg_off is not monotone or runs past msgs_len"; return -(int32_t)hipErrorInvalidValue; }
-    if (bad_scalar) { ctx->err = "verify_batch: internal error (batch scalar with bit 255 set)"; return -(int32_t)hipErrorInvalidValue; }
+    if (bad_off) return bad_arg(ctx, "verify_batch: msg_off is not monotone or runs past msgs_len");
+    if (bad_scalar) return bad_arg(ctx, "verify_batch: internal error (batch scalar with bit 255 set)");
     return seen[C25519_NONE] ? C25519_NONE : seen[C25519_SCALAR_FORMAT] ? C25519_SCALAR_FORMAT : seen[C25519_VERIFY] ? C25519_VERIFY : C25519_OK;
 }
 
@@ -962,8 +957,8 @@ EXPORT int32_t ed25519_verify_batch_keys(c25519_ctx *ctx, const uint8_t *msgs, c
                                          const uint8_t *pk_points, uint64_t n, uint32_t z_mode) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
-    if (z_mode > 1) { ctx->err = "verify_batch: bad z_mode"; return -(int32_t)hipErrorInvalidValue; }
-    if (!offsets_ok(msg_off, n)) { ctx->err = "verify_batch: msg_off is not monotone"; return -(int32_t)hipErrorInvalidValue; }
+    if (z_mode > 1) return bad_arg(ctx, "verify_batch: bad z_mode");
+    if (!offsets_ok(msg_off, n)) return bad_arg(ctx, "verify_batch: msg_off is not monotone");
     const uint64_t mlen = msg_off[n];
     int32_t r;
     if (2 * n + 1 <= small_upload_max_terms() && mlen <= (1u << 20)) {
@@ -1036,7 +1031,7 @@ EXPORT int32_t c25519_debug_batch_zs(c25519_ctx *ctx, const uint8_t *msgs, const
                                      uint32_t z_mode, uint8_t *out_z16) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
-    if (n > VERIFY_PASS_MAX || z_mode > 2 || !offsets_ok(msg_off, n)) { ctx->err = "debug_batch_zs: bad arguments"; return -(int32_t)hipErrorInvalidValue; }
+    if (n > VERIFY_PASS_MAX || z_mode > 2 || !offsets_ok(msg_off, n)) return bad_arg(ctx, "debug_batch_zs: bad arguments");
     if (z_mode == 2) {
         // the device z-mode's values computed by the HOST restatement (ztree_host_zs): must equal z_mode 1 byte for byte
         std::vector<uint8_t> hred(n * 32), z((n + 4) * 16);

@@ -46,6 +46,119 @@ def select_library(path):
     _LIB_OVERRIDE = path
 
 
+# every exported entry point of include/c25519_hip.h: name -> (restype, argtypes)
+_vp, _u64, _i32 = C.c_void_p, C.c_uint64, C.c_int32
+_SIGS = {
+    "c25519_ctx_create": (_vp, [C.c_int, C.c_uint32]),
+    "c25519_ctx_destroy": (None, [_vp]),
+    "c25519_ctx_set_stream": (_i32, [_vp, _vp]),
+    "c25519_ctx_synchronize": (_i32, [_vp]),
+    "c25519_last_error": (C.c_char_p, [_vp]),
+    "c25519_last_kernel_ms": (C.c_float, [_vp]),
+    "c25519_phase_ms": (C.c_float, [_vp, C.c_uint32, C.c_int]),
+    "c25519_last_call_phase_ms": (C.c_float, [_vp, C.c_int, _vp]),
+    "c25519_debug_batch_zs": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32, _vp]),
+    "c25519_debug_sort": (_i32, [_vp, _vp, _u64, _u64, C.c_int32]),
+    "c25519_mul_base_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_mul_base_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_mul_base_batch_vartime_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_mul_base_clamped_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_mul_base_clamped_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_basetable_create": (_vp, [_vp, _vp, C.c_int]),
+    "c25519_basetable_destroy": (None, [_vp, _vp]),
+    "c25519_mul_table_batch_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_mul_table_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_x25519_contributory_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "c25519_x25519_contributory_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "c25519_mul_clamped_batch_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_mul_clamped_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_point_order_checks_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
+    "c25519_point_order_checks_batch": (_i32, [_vp, _vp, _u64, C.c_int, C.c_int, _vp]),
+    "c25519_host_alloc": (_vp, [C.c_size_t]),
+    "c25519_host_free": (None, [_vp]),
+    "c25519_last_ffi_ms": (C.c_double, [_vp, _vp, _vp]),
+    "c25519_ctx_trim": (_i32, [_vp]),
+    "c25519_last_kernel_name": (C.c_char_p, [_vp, C.c_int]),
+    "c25519_x25519_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "c25519_x25519_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "c25519_x25519_base_batch_dev": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_x25519_base_batch": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_decompress_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_decompress_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_compress_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_compress_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_to_montgomery_batch_dev": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_to_montgomery_batch": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_msm_vartime_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
+    "c25519_msm_vartime": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
+    "c25519_msm_partial_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_fold_partials": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_msm_partial_record_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_fold_partial_records": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_partial_record_pack": (_i32, [_vp, _i32, _vp, _vp]),
+    "ed25519_batch_hram_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "ed25519_batch_transcript_zs": (_i32, [_vp, _vp, _u64, _vp]),
+    "ed25519_verify_batch_record_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "ed25519_fold_verify_records": (_i32, [_vp, _vp, _u64]),
+    "c25519_msm_vartime_multi": (_i32, [_vp, _i32, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
+    "ed25519_verify_batch_multi": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _u64, C.c_uint32]),
+    "ed25519_verify_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, C.c_uint32]),
+    "ed25519_verify_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32]),
+    "ed25519_verify_batch_keys_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_uint32]),
+    "ed25519_verify_batch_keys": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, C.c_uint32]),
+    "c25519_mul_batch_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_mul_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_double_base_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_double_base_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_last_call_host_us": (_i32, [_vp, _vp]),
+    "c25519_ctx_counter": (_u64, [_vp, _i32]),
+    "ed25519_verify_each_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, C.c_int, _vp]),
+    "ed25519_verify_each": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, C.c_int, _vp]),
+    "ed25519_verify_each_prehashed_dev": (_i32, [_vp, _vp, C.c_char_p, C.c_uint32, _vp, _vp, _u64, C.c_int, _vp]),
+    "ed25519_verify_each_prehashed": (_i32, [_vp, _vp, C.c_char_p, C.c_uint32, _vp, _vp, _u64, C.c_int, _vp]),
+    "ed25519_sign_batch_prehashed_dev": (_i32, [_vp, _vp, _vp, C.c_char_p, C.c_uint32, _u64, _vp, _vp]),
+    "ed25519_sign_batch_prehashed": (_i32, [_vp, _vp, _vp, C.c_char_p, C.c_uint32, _u64, _vp, _vp]),
+    "ed25519_keygen_batch_dev": (_i32, [_vp, _vp, _u64, _vp]),
+    "ed25519_sign_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "ed25519_sign_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "c25519_precomp_create": (_vp, [_vp, _vp, _u64, C.c_int]),
+    "c25519_precomp_destroy": (None, [_vp, _vp]),
+    "c25519_precomp_len": (_u64, [_vp]),
+    "c25519_precomp_msm_vartime": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
+    "c25519_msm_consttime": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
+    "c25519_double_and_compress_batch_dev": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_double_and_compress_batch": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_scalar_invert_batch": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_ristretto_from_uniform_bytes_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_ristretto_from_uniform_bytes_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_ristretto_map_to_curve_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_ristretto_map_to_curve_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_ristretto_hash_from_bytes_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, C.c_int, _vp]),
+    "c25519_ristretto_hash_from_bytes_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_edwards_hash_to_curve_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, C.c_char_p, C.c_uint32, C.c_int, C.c_int, _vp]),
+    "c25519_edwards_hash_to_curve_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_char_p, C.c_uint32, C.c_int, C.c_int, _vp]),
+    "c25519_ristretto_lizard_encode_sha256_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_ristretto_lizard_encode_sha256_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp]),
+    "c25519_ristretto_lizard_decode_sha256_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_ristretto_lizard_decode_sha256_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_ristretto_map_to_curve_inverse_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _vp, _vp]),
+    "c25519_ristretto_map_to_curve_inverse_batch": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _vp, _vp]),
+    "c25519_montgomery_mul_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "c25519_montgomery_mul_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "c25519_montgomery_mul_bits_be_batch_dev": (_i32, [_vp, _vp, C.c_uint32, _vp, _u64, _vp]),
+    "c25519_montgomery_mul_bits_be_batch": (_i32, [_vp, _vp, C.c_uint32, _vp, _u64, _vp]),
+    "c25519_montgomery_mul_base_batch_dev": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_montgomery_mul_base_batch": (_i32, [_vp, _vp, _u64, _vp]),
+    "c25519_montgomery_to_edwards_batch_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_montgomery_to_edwards_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_microbench": (C.c_double, [_vp, C.c_int, C.c_int]),
+    "c25519_selftest_field": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _u64, _vp]),
+    "c25519_selftest_scalar": (_i32, [_vp, C.c_int, _vp, _vp, _u64, _vp]),
+    "c25519_msm_geometry": (_i32, [_u64, _vp, _vp, _vp, _vp, _vp]),
+}
+ABI_SYMBOLS = list(_SIGS)
+
+
 def load_library():
     """Load the HIP library (after torch, so both share one HIP runtime).  Raises if absent."""
     global _LIB
@@ -60,149 +173,12 @@ def load_library():
     except Exception:  # pragma: no cover
         pass
     lib = C.CDLL(path)
-    vp, u64, i32 = C.c_void_p, C.c_uint64, C.c_int32
-    sigs = {
-        "c25519_ctx_create": (vp, [C.c_int, C.c_uint32]),
-        "c25519_ctx_destroy": (None, [vp]),
-        "c25519_ctx_set_stream": (i32, [vp, vp]),
-        "c25519_ctx_synchronize": (i32, [vp]),
-        "c25519_last_error": (C.c_char_p, [vp]),
-        "c25519_last_kernel_ms": (C.c_float, [vp]),
-        "c25519_phase_ms": (C.c_float, [vp, C.c_uint32, C.c_int]),
-        "c25519_last_call_phase_ms": (C.c_float, [vp, C.c_int, vp]),
-        "c25519_debug_batch_zs": (i32, [vp, vp, vp, vp, vp, u64, C.c_uint32, vp]),
-        "c25519_debug_sort": (i32, [vp, vp, u64, u64, C.c_int32]),
-        "c25519_mul_base_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_mul_base_batch": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_mul_base_batch_vartime_dev": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_mul_base_clamped_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_mul_base_clamped_batch": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_basetable_create": (vp, [vp, vp, C.c_int]),
-        "c25519_basetable_destroy": (None, [vp, vp]),
-        "c25519_mul_table_batch_dev": (i32, [vp, vp, vp, u64, C.c_int, vp]),
-        "c25519_mul_table_batch": (i32, [vp, vp, vp, u64, C.c_int, vp]),
-        "c25519_x25519_contributory_batch_dev": (i32, [vp, vp, vp, u64, vp, vp]),
-        "c25519_x25519_contributory_batch": (i32, [vp, vp, vp, u64, vp, vp]),
-        "c25519_mul_clamped_batch_dev": (i32, [vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]),
-        "c25519_mul_clamped_batch": (i32, [vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]),
-        "c25519_point_order_checks_batch_dev": (i32, [vp, vp, u64, C.c_int, C.c_int, vp]),
-        "c25519_point_order_checks_batch": (i32, [vp, vp, u64, C.c_int, C.c_int, vp]),
-        "c25519_host_alloc": (vp, [C.c_size_t]),
-        "c25519_host_free": (None, [vp]),
-        "c25519_last_ffi_ms": (C.c_double, [vp, vp, vp]),
-        "c25519_ctx_trim": (i32, [vp]),
-        "c25519_last_kernel_name": (C.c_char_p, [vp, C.c_int]),
-        "c25519_x25519_batch_dev": (i32, [vp, vp, vp, u64, vp]),
-        "c25519_x25519_batch": (i32, [vp, vp, vp, u64, vp]),
-        "c25519_x25519_base_batch_dev": (i32, [vp, vp, u64, vp]),
-        "c25519_x25519_base_batch": (i32, [vp, vp, u64, vp]),
-        "c25519_decompress_batch_dev": (i32, [vp, vp, u64, C.c_int, vp, vp]),
-        "c25519_decompress_batch": (i32, [vp, vp, u64, C.c_int, vp, vp]),
-        "c25519_compress_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_compress_batch": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_to_montgomery_batch_dev": (i32, [vp, vp, u64, vp]),
-        "c25519_to_montgomery_batch": (i32, [vp, vp, u64, vp]),
-        "c25519_msm_vartime_dev": (i32, [vp, vp, vp, u64, C.c_int, C.c_int, vp]),
-        "c25519_msm_vartime": (i32, [vp, vp, vp, u64, C.c_int, C.c_int, vp]),
-        "c25519_msm_partial_dev": (i32, [vp, vp, vp, u64, C.c_int, vp]),
-        "c25519_fold_partials": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_msm_partial_record_dev": (i32, [vp, vp, vp, u64, C.c_int, vp]),
-        "c25519_fold_partial_records": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_partial_record_pack": (i32, [vp, i32, vp, vp]),
-        "ed25519_batch_hram_dev": (i32, [vp, vp, vp, u64, vp, vp, u64, vp]),
-        "ed25519_batch_transcript_zs": (i32, [vp, vp, u64, vp]),
-        "ed25519_verify_batch_record_dev": (i32, [vp, vp, vp, vp, vp, vp, u64, vp]),
-        "ed25519_fold_verify_records": (i32, [vp, vp, u64]),
-        "c25519_msm_vartime_multi": (i32, [vp, i32, vp, vp, u64, C.c_int, C.c_int, vp]),
-        "ed25519_verify_batch_multi": (i32, [vp, i32, vp, vp, vp, vp, u64, C.c_uint32]),
-        "ed25519_verify_batch_dev": (i32, [vp, vp, vp, u64, vp, vp, u64, C.c_uint32]),
-        "ed25519_verify_batch": (i32, [vp, vp, vp, vp, vp, u64, C.c_uint32]),
-        "ed25519_verify_batch_keys_dev": (i32, [vp, vp, vp, u64, vp, vp, vp, u64, C.c_uint32]),
-        "ed25519_verify_batch_keys": (i32, [vp, vp, vp, vp, vp, vp, u64, C.c_uint32]),
-        "c25519_mul_batch_dev": (i32, [vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]),
-        "c25519_mul_batch": (i32, [vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]),
-        "c25519_double_base_batch_dev": (i32, [vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]),
-        "c25519_double_base_batch": (i32, [vp, vp, vp, vp, u64, C.c_int, C.c_int, vp, vp]),
-        "c25519_last_call_host_us": (i32, [vp, vp]),
-        "c25519_ctx_counter": (u64, [vp, i32]),
-        "ed25519_verify_each_dev": (i32, [vp, vp, vp, u64, vp, vp, u64, C.c_int, vp]),
-        "ed25519_verify_each": (i32, [vp, vp, vp, vp, vp, u64, C.c_int, vp]),
-        "ed25519_verify_each_prehashed_dev": (i32, [vp, vp, C.c_char_p, C.c_uint32, vp, vp, u64, C.c_int, vp]),
-        "ed25519_verify_each_prehashed": (i32, [vp, vp, C.c_char_p, C.c_uint32, vp, vp, u64, C.c_int, vp]),
-        "ed25519_sign_batch_prehashed_dev": (i32, [vp, vp, vp, C.c_char_p, C.c_uint32, u64, vp, vp]),
-        "ed25519_sign_batch_prehashed": (i32, [vp, vp, vp, C.c_char_p, C.c_uint32, u64, vp, vp]),
-        "ed25519_keygen_batch_dev": (i32, [vp, vp, u64, vp]),
-        "ed25519_sign_batch_dev": (i32, [vp, vp, vp, vp, u64, u64, vp, vp]),
-        "ed25519_sign_batch": (i32, [vp, vp, vp, vp, u64, vp, vp]),
-        "c25519_precomp_create": (vp, [vp, vp, u64, C.c_int]),
-        "c25519_precomp_destroy": (None, [vp, vp]),
-        "c25519_precomp_len": (u64, [vp]),
-        "c25519_precomp_msm_vartime": (i32, [vp, vp, vp, u64, vp, vp, u64, C.c_int, C.c_int, vp]),
-        "c25519_msm_consttime": (i32, [vp, vp, vp, u64, C.c_int, C.c_int, vp]),
-        "c25519_double_and_compress_batch_dev": (i32, [vp, vp, u64, vp]),
-        "c25519_double_and_compress_batch": (i32, [vp, vp, u64, vp]),
-        "c25519_scalar_invert_batch": (i32, [vp, vp, u64, vp]),
-        "c25519_ristretto_from_uniform_bytes_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_ristretto_from_uniform_bytes_batch": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_ristretto_map_to_curve_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_ristretto_map_to_curve_batch": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_ristretto_hash_from_bytes_batch_dev": (i32, [vp, vp, vp, u64, u64, C.c_int, vp]),
-        "c25519_ristretto_hash_from_bytes_batch": (i32, [vp, vp, vp, u64, C.c_int, vp]),
-        "c25519_edwards_hash_to_curve_batch_dev": (i32, [vp, vp, vp, u64, u64, C.c_char_p, C.c_uint32, C.c_int, C.c_int, vp]),
-        "c25519_edwards_hash_to_curve_batch": (i32, [vp, vp, vp, u64, C.c_char_p, C.c_uint32, C.c_int, C.c_int, vp]),
-        "c25519_ristretto_lizard_encode_sha256_batch_dev": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_ristretto_lizard_encode_sha256_batch": (i32, [vp, vp, u64, C.c_int, vp]),
-        "c25519_ristretto_lizard_decode_sha256_batch_dev": (i32, [vp, vp, u64, C.c_int, vp, vp]),
-        "c25519_ristretto_lizard_decode_sha256_batch": (i32, [vp, vp, u64, C.c_int, vp, vp]),
-        "c25519_ristretto_map_to_curve_inverse_batch_dev": (i32, [vp, vp, u64, C.c_int, vp, vp, vp]),
-        "c25519_ristretto_map_to_curve_inverse_batch": (i32, [vp, vp, u64, C.c_int, vp, vp, vp]),
-        "c25519_montgomery_mul_batch_dev": (i32, [vp, vp, vp, u64, vp]),
-        "c25519_montgomery_mul_batch": (i32, [vp, vp, vp, u64, vp]),
-        "c25519_montgomery_mul_bits_be_batch_dev": (i32, [vp, vp, C.c_uint32, vp, u64, vp]),
-        "c25519_montgomery_mul_bits_be_batch": (i32, [vp, vp, C.c_uint32, vp, u64, vp]),
-        "c25519_montgomery_mul_base_batch_dev": (i32, [vp, vp, u64, vp]),
-        "c25519_montgomery_mul_base_batch": (i32, [vp, vp, u64, vp]),
-        "c25519_montgomery_to_edwards_batch_dev": (i32, [vp, vp, vp, u64, C.c_int, vp, vp]),
-        "c25519_montgomery_to_edwards_batch": (i32, [vp, vp, vp, u64, C.c_int, vp, vp]),
-        "c25519_microbench": (C.c_double, [vp, C.c_int, C.c_int]),
-        "c25519_selftest_field": (i32, [vp, C.c_int, C.c_int, vp, vp, u64, vp]),
-        "c25519_selftest_scalar": (i32, [vp, C.c_int, vp, vp, u64, vp]),
-        "c25519_msm_geometry": (i32, [u64, vp, vp, vp, vp, vp]),
-    }
-    for name, (res, args) in sigs.items():
+    for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not export the ABI
         fn.restype, fn.argtypes = res, args
     _LIB = lib
     return lib
 
-
-ABI_SYMBOLS = [
-    "c25519_ctx_create", "c25519_ctx_destroy", "c25519_ctx_set_stream", "c25519_ctx_synchronize", "c25519_last_error",
-    "c25519_mul_base_clamped_batch_dev", "c25519_mul_base_clamped_batch", "c25519_basetable_create", "c25519_basetable_destroy", "c25519_mul_table_batch_dev",
-    "c25519_mul_table_batch", "c25519_x25519_contributory_batch_dev", "c25519_x25519_contributory_batch", "c25519_mul_clamped_batch_dev", "c25519_mul_clamped_batch",
-    "c25519_point_order_checks_batch_dev", "c25519_point_order_checks_batch",
-    "c25519_host_alloc", "c25519_host_free", "c25519_last_ffi_ms", "c25519_ctx_trim", "c25519_last_kernel_name",
-    "c25519_last_kernel_ms", "c25519_phase_ms", "c25519_last_call_phase_ms", "c25519_debug_batch_zs", "c25519_debug_sort", "c25519_mul_base_batch_dev", "c25519_mul_base_batch_vartime_dev", "c25519_mul_base_batch", "c25519_x25519_batch_dev",
-    "c25519_x25519_batch", "c25519_x25519_base_batch_dev", "c25519_x25519_base_batch", "c25519_decompress_batch_dev", "c25519_decompress_batch", "c25519_compress_batch_dev",
-    "c25519_compress_batch", "c25519_msm_vartime_dev", "c25519_msm_vartime", "c25519_msm_partial_dev",
-    "c25519_fold_partials", "c25519_msm_partial_record_dev", "c25519_fold_partial_records", "c25519_partial_record_pack",
-    "ed25519_batch_hram_dev", "ed25519_batch_transcript_zs", "ed25519_verify_batch_record_dev", "ed25519_fold_verify_records", "c25519_msm_vartime_multi", "ed25519_verify_batch_multi", "ed25519_verify_batch_dev", "ed25519_verify_batch", "ed25519_verify_batch_keys_dev", "ed25519_verify_batch_keys", "c25519_microbench", "c25519_selftest_field", "c25519_selftest_scalar", "c25519_msm_geometry",
-    "c25519_mul_batch_dev", "c25519_mul_batch", "c25519_double_base_batch_dev", "c25519_double_base_batch", "ed25519_verify_each_dev", "ed25519_verify_each",
-    "ed25519_keygen_batch_dev", "ed25519_sign_batch_dev", "ed25519_sign_batch",
-    "c25519_last_call_host_us", "c25519_ctx_counter", "ed25519_verify_each_prehashed_dev", "ed25519_verify_each_prehashed", "ed25519_sign_batch_prehashed_dev", "ed25519_sign_batch_prehashed",
-    "c25519_to_montgomery_batch_dev", "c25519_to_montgomery_batch",
-    "c25519_precomp_create", "c25519_precomp_destroy", "c25519_precomp_len", "c25519_precomp_msm_vartime",
-    "c25519_msm_consttime", "c25519_double_and_compress_batch_dev", "c25519_double_and_compress_batch",
-    "c25519_scalar_invert_batch",
-    "c25519_ristretto_from_uniform_bytes_batch_dev", "c25519_ristretto_from_uniform_bytes_batch", "c25519_ristretto_map_to_curve_batch_dev",
-    "c25519_ristretto_map_to_curve_batch", "c25519_ristretto_hash_from_bytes_batch_dev", "c25519_ristretto_hash_from_bytes_batch",
-    "c25519_edwards_hash_to_curve_batch_dev", "c25519_edwards_hash_to_curve_batch",
-    "c25519_ristretto_lizard_encode_sha256_batch_dev", "c25519_ristretto_lizard_encode_sha256_batch",
-    "c25519_ristretto_lizard_decode_sha256_batch_dev", "c25519_ristretto_lizard_decode_sha256_batch",
-    "c25519_ristretto_map_to_curve_inverse_batch_dev", "c25519_ristretto_map_to_curve_inverse_batch",
-    "c25519_montgomery_mul_batch_dev", "c25519_montgomery_mul_batch", "c25519_montgomery_mul_bits_be_batch_dev", "c25519_montgomery_mul_bits_be_batch",
-    "c25519_montgomery_mul_base_batch_dev", "c25519_montgomery_mul_base_batch", "c25519_montgomery_to_edwards_batch_dev", "c25519_montgomery_to_edwards_batch",
-]
 
 _PT = {FMT_EDWARDS_Y: 32, FMT_RISTRETTO: 32, FMT_RAW160: 160}
 PARTIAL_RECORD_BYTES = 9024      # C25519_PARTIAL_RECORD_BYTES

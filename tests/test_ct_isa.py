@@ -12,34 +12,13 @@ of k_mul_base<5, CT>).  So the property is asserted on the instruction stream:
   * the ladder loop of k_x25519: no exec-mask branch, and conditional swaps as v_cndmask."""
 import os
 import re
-import shutil
-import subprocess
 from collections import Counter
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "curve25519-dalek_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from util import HIPCC, asm_functions as _functions, device_asm as _asm
+
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-
-
-def _asm(tmp_path_factory, name):
-    out = tmp_path_factory.mktemp("isa") / (name + ".s")
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out), os.path.join(CSRC, name + ".hip")],
-                   check=True, capture_output=True, timeout=900)
-    return open(out).read().split("\n")
-
-
-def _functions(lines, pattern):
-    """-> {mangled name: body lines} for every function whose label matches"""
-    out = {}
-    for i, l in enumerate(lines):
-        m = re.match(r"^(" + pattern + r"\S*):", l)
-        if m:
-            end = next(j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end"))
-            out[m.group(1)] = lines[i:end]
-    return out
 
 
 def _loops(body):

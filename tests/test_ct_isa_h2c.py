@@ -8,34 +8,22 @@ the bounds exit (one s_and_saveexec and one branch on exec), and there is no bra
 (scalar, SCC) loops of the exponentiation chains.  No data-dependent memory address exists in these kernels: item i reads and
 writes its own slots only."""
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "curve25519-dalek_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from util import HIPCC, asm_functions, asm_ops, device_asm
+
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 
 
 @pytest.fixture(scope="module")
 def h2c_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "h2c.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out), os.path.join(CSRC, "h2c.hip")],
-                   check=True, capture_output=True, timeout=900)
-    return open(out).read().split("\n")
+    return device_asm(tmp_path_factory, "h2c")
 
 
 def _functions(lines, pattern):
-    out = {}
-    for i, l in enumerate(lines):
-        m = re.match(r"^(" + pattern + r"\S*):", l)
-        if m:
-            end = next(j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end"))
-            out[m.group(1)] = [x.split()[0] for x in lines[i + 1:end] if re.match(r"^\s+[a-z]", x)]
-    return out
+    """-> {mangled name: opcodes} of the matching functions"""
+    return {name: asm_ops(body) for name, body in asm_functions(lines, pattern).items()}
 
 
 @pytest.mark.parametrize("kernel", ["k_ristretto_from_uniform", "k_ristretto_map"])

@@ -7,39 +7,23 @@ there is no branch on vcc (which would follow per-lane data), every other branch
 traffic and no call.  The mul_bits_be loop must be counted in SGPRs: its trip count is the kernel argument nbits, never lane data."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "curve25519-dalek_amd", "csrc")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from util import HIPCC, asm_functions, asm_ops as _ops, device_asm
+
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 KERNELS = [("k_mont_mul", 1, 1200), ("k_mont_mul_bits", 1, 1200), ("k_mont_to_edwards_prep", 1, 40), ("k_mont_to_edwards", 4, 5000)]
 
 
 @pytest.fixture(scope="module")
 def mont_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "montgomery.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out), os.path.join(CSRC, "montgomery.hip")],
-                   check=True, capture_output=True, timeout=900)
-    return open(out).read().split("\n")
+    return device_asm(tmp_path_factory, "montgomery")
 
 
 def _functions(lines, kernel):
     """{mangled name: [lines of the body]} of the kernel's instantiations"""
-    out = {}
-    for i, l in enumerate(lines):
-        m = re.match(r"^(_ZN6c25519\d+" + kernel + r"(?:E|I)\S*):", l)
-        if m:
-            end = next(j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end"))
-            out[m.group(1)] = lines[i + 1:end]
-    return out
-
-
-def _ops(body):
-    return [x.split()[0] for x in body if re.match(r"^\s+[a-z]", x)]
+    return asm_functions(lines, r"_ZN6c25519\d+" + kernel + r"(?:E|I)")
 
 
 @pytest.mark.parametrize("kernel,count,min_ops", KERNELS)

@@ -1,5 +1,8 @@
 """Shared helpers for the GPU parity tests: seeded input generators (numpy) and oracle batch calls."""
 import os
+import re
+import shutil
+import subprocess
 
 import numpy as np
 
@@ -49,3 +52,32 @@ def edge_scalars():
     vals += [(1 << k) for k in range(0, 255, 17)] + [(1 << k) - 1 for k in range(5, 255, 23)]
     vals += [sum(32 << (6 * i) for i in range(42)), sum(31 << (6 * i) for i in range(42)), sum(63 << (6 * i) for i in range(42))]
     return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32)
+
+
+# ---- the compiled gfx950 code of a source file, for the ISA tests (hipcc -S, no GPU needed) ----------------------------------------------------------
+CSRC = os.path.join(ROOT, "curve25519-dalek_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def device_asm(tmp_path_factory, name):
+    """-> the lines of the gfx950 assembly of csrc/<name>.hip (release flags, device code only)"""
+    out = tmp_path_factory.mktemp("isa") / (name + ".s")
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out), os.path.join(CSRC, name + ".hip")],
+                   check=True, capture_output=True, timeout=900)
+    return open(out).read().split("\n")
+
+
+def asm_functions(lines, pattern):
+    """-> {mangled name: body lines after the label} for every function whose label matches `pattern`"""
+    out = {}
+    for i, l in enumerate(lines):
+        m = re.match(r"^(" + pattern + r"\S*):", l)
+        if m:
+            end = next(j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end"))
+            out[m.group(1)] = lines[i + 1:end]
+    return out
+
+
+def asm_ops(body):
+    """-> the opcodes of the instructions in `body`"""
+    return [x.split()[0] for x in body if re.match(r"^\s+[a-z]", x)]
