@@ -12,12 +12,19 @@ partial sum per rank over RCCL, then the fold): strong scaling, as configs[3] an
 GPU); under a launcher (RANK / WORLD_SIZE set, the driver's way) it just joins.  On a box with fewer than N GPUs it
 fails loudly.
 
-At N = 1 the same line carries, as `sub`, the other BASELINE configurations timed the same way (K steps after W warmup
-steps each, their own HIP-event kernel timings): configs[2] verify_batch of 2^20 signatures (VerifyingKey mode, device
-z-mode; plus the strict-transcript z-mode at 2^14 and 2^20), configs[1] 2^20 fixed-base multiplications (radix-2^16
-tables and the constant-time lookups), configs[4] 2^20 X25519 ladders -- each with its own `roofline`, `valu` and
-`cpu_baseline` objects -- and, as `ffi_path`, the same workloads through the HOST-POINTER entry points a Rust caller binds
-(wall-clock per call, units/s, achieved PCIe GB/s against the link peak).  `--workload X` makes X the headline and drops both.
+A plain run does what the headline needs and no more: set-up, the first call (its status checked), the clock warm-up
+probe, W warm-up steps, K timed steps, `--dump-outputs`, the line (with the `roofline` object of the timed steps' own
+HIP events).  Everything else is `--full`:
+- the full-size MSM checked against (sum x_i y_i) B, and the `cpu_baseline` object (the C restatement of the reference,
+  parity-checked against the GPU output); `--no-cpu-baseline` drops the latter;
+- at N = 1, as `sub`, the other BASELINE configurations timed the same way (K steps after W warmup steps each, their own
+  HIP-event kernel timings): configs[2] verify_batch of 2^20 signatures (VerifyingKey mode, device z-mode; plus the
+  strict-transcript z-mode at 2^14 and 2^20), configs[1] 2^20 fixed-base multiplications (radix-2^16 tables and the
+  constant-time lookups), configs[4] 2^20 X25519 ladders -- each with its own `roofline`, `valu` and `cpu_baseline`
+  objects -- with `scale_model`, `small_n`, `mid_n` and, as `ffi_path`, the same workloads through the HOST-POINTER
+  entry points a Rust caller binds (wall-clock per call, units/s, achieved PCIe GB/s against the link peak); `--no-sub`
+  or `--workload X` (X the headline) drops these;
+- under a launcher, `multi_gpu.model` (the fold of N records measured alone beside the step it predicts).
 """
 import argparse
 import glob
@@ -166,13 +173,16 @@ class Workload:
         self.run = run
 
     # -- product-only sanity outside the timed region (the CPU restatement is used ONLY in cpu_baseline()) -------------
-    def self_check(self):
+    def self_check(self, full=True):
+        """The first call, outside the timed region, and its status; with `full` (bench.py --full) the MSM is also checked against (sum x_i y_i) B."""
         torch, eng, E = self.torch, self.eng, self.pkg.engine
         self.run()
         torch.cuda.synchronize(self.dev)
         if self.name == "verify" and self.result["st"] != 0:
             raise SystemExit("SELF-CHECK FAILURE: valid batch rejected (status %d)" % self.result["st"])
-        if self.name == "msm":
+        if self.name == "msm" and not full:
+            del self.ys
+        elif self.name == "msm":
             # (sum x_i y_i mod l) * B through the fixed-base kernel must equal this rank's partial MSM over P_i = y_i * B
             def limbs(t):
                 return (t.view(torch.int16).to(torch.int64) & 0xFFFF)
@@ -674,11 +684,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: as many as make the timed region >= 2 s, at least 10)")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--workload", default=None, choices=sorted(ALGO), help="make this the headline and report it alone (default: msm + the others as `sub`)")
+    ap.add_argument("--workload", default=None, choices=sorted(ALGO), help="make this the headline and report it alone (default: msm, with --full the others as `sub`)")
     ap.add_argument("--log2n", type=int, default=None, help="units = 2^log2n (default: the BASELINE size; msm: TOTAL terms under --scaling strong)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"], help="N > 1, msm: 2^24 terms in total (strong, configs[3]) or per GPU (weak)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sub", action="store_true", help="headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the full-size MSM check, the CPU baseline, the other configurations (`sub`), scale_model, small_n, mid_n, "
+                         "ffi_path and the multi-GPU step model (default: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-sub", action="store_true", help="--full without the other configurations")
     ap.add_argument("--z-mode", default="device", choices=["device", "transcript"], help="verify headline: z derivation")
     ap.add_argument("--fixed-base-variant", default="ct", choices=["ct", "vartime"], help="fixed_base headline: ct = constant-time table lookups (the reference's mul_base semantics), vartime = radix-2^16 tables (public scalars)")
     ap.add_argument("--keys-as-bytes", action="store_true",
@@ -749,11 +762,12 @@ def main():
 
     w.force_collective = use_dist
     clock_hz = float(getattr(torch.cuda.get_device_properties(dev), "clock_rate", 2400000)) * 1e3      # kHz -> Hz (MI355X: 2.4 GHz)
-    w.self_check()
+    w.self_check(args.full)
     # live peak of the binding unit on THIS box (box-to-box spread is ~6 %): v_mad_u64_u32 issue rate, measured right
     # before the timed steps by the library's own probe kernel (c25519_microbench, kernels.hip), best of 100 runs.
     # The ~60 ms of full-rate integer work also bring the GPU from its idle clock to the sustained one (measured: the
-    # probe reads 27 T/s cold and 33 T/s after ~50 ms), so a short --steps measures steady-state throughput, not the ramp.
+    # probe reads 27 T/s cold and 33 T/s after ~50 ms), so a short --steps measures steady-state throughput, not the ramp:
+    # a plain run keeps the probe for that, and its roofline object costs nothing more.
     probes = int(os.environ.get("C25519_BENCH_PROBES", "100"))
     mac_peak = max(eng.microbench(0, 4000) for _ in range(probes)) * 1e9
 
@@ -798,24 +812,25 @@ def main():
         vmin = v.clone()
         dist.all_reduce(v, op=dist.ReduceOp.MAX); dist.all_reduce(vmin, op=dist.ReduceOp.MIN)
         mx, mn = v.tolist(), vmin.tolist()
-        import numpy as np
-        rec1 = eng.msm_partial_record_t(w.xs[:1 << 12].contiguous(), w.pts[:1 << 12].contiguous(), E.FMT_RAW160).cpu().numpy()
-        recs = np.ascontiguousarray(np.tile(rec1.reshape(1, -1), (world, 1)))
-        ts = []
-        for _ in range(7):
-            c0 = time.perf_counter(); E.fold_partial_records(recs, E.FMT_EDWARDS_Y); ts.append((time.perf_counter() - c0) * 1e3)
-        fold_alone = sorted(ts)[len(ts) // 2]
         multi_gpu = {"what": "per step, mean over the timed steps: max (min) over ranks of this rank's shard on its GPU [HIP events on the launch stream], the all_gather of the records "
                              "[events around all_gather_into_tensor], and the rest of the call (read-back of N records + host fold + launch latency); sum_ms = the call's wall-clock",
                      "shard_ms": mx[0], "collective_ms": mx[1], "d2h_fold_ms": mx[2], "sum_ms": mx[3],
                      "min_over_ranks": {"shard_ms": mn[0], "collective_ms": mn[1], "d2h_fold_ms": mn[2], "sum_ms": mn[3]},
-                     "ranks_seen_by_rccl": rccl_ranks, "rccl_warmup_collectives_outside_timed_region": 2 + args.warmup,
-                     "model": {"shard_ms": mx[0], "fold_of_N_records_alone_ms": fold_alone, "exchange_ms_assumed_by_scale_model": 0.05,
-                               "predicted_step_ms": mx[0] + fold_alone + 0.05,
-                               "how": "scale_model (the N = 1 line) predicts step(N) = shard(2^24 / N terms on one GPU) + fold(N records) + 0.05 ms assumed for the exchange: "
-                                      "compare collective_ms with the 0.05 and d2h_fold_ms with the fold measured alone"}}
+                     "ranks_seen_by_rccl": rccl_ranks, "rccl_warmup_collectives_outside_timed_region": 2 + args.warmup}
+        if args.full:
+            import numpy as np
+            rec1 = eng.msm_partial_record_t(w.xs[:1 << 12].contiguous(), w.pts[:1 << 12].contiguous(), E.FMT_RAW160).cpu().numpy()
+            recs = np.ascontiguousarray(np.tile(rec1.reshape(1, -1), (world, 1)))
+            ts = []
+            for _ in range(7):
+                c0 = time.perf_counter(); E.fold_partial_records(recs, E.FMT_EDWARDS_Y); ts.append((time.perf_counter() - c0) * 1e3)
+            fold_alone = sorted(ts)[len(ts) // 2]
+            multi_gpu["model"] = {"shard_ms": mx[0], "fold_of_N_records_alone_ms": fold_alone, "exchange_ms_assumed_by_scale_model": 0.05,
+                                  "predicted_step_ms": mx[0] + fold_alone + 0.05,
+                                  "how": "scale_model (the N = 1 line) predicts step(N) = shard(2^24 / N terms on one GPU) + fold(N records) + 0.05 ms assumed for the exchange: "
+                                         "compare collective_ms with the 0.05 and d2h_fold_ms with the fold measured alone"}
 
-    want_cpu = (rank == 0 and world == 1 and not args.no_cpu_baseline)
+    want_cpu = (rank == 0 and world == 1 and args.full and not args.no_cpu_baseline)
     budget = float(os.environ.get("C25519_BENCH_CPU_S", "10"))
     res = None
     if rank == 0:
@@ -829,7 +844,7 @@ def main():
         dist.barrier()
 
     # ---- the other BASELINE configurations, N = 1 only ----------------------------------------------------------------
-    if rank == 0 and world == 1 and args.workload is None and not args.no_sub:
+    if rank == 0 and world == 1 and args.workload is None and args.full and not args.no_sub:
         res["scale_model"] = scale_model(w, eng, pkg, torch, dev, res["ms_per_step"])
         del w
         torch.cuda.empty_cache()

@@ -11,8 +11,8 @@ mkdir -p $OUT $RAW $R/gpurun_out/raw
 cd $R
 python tools/probes.py > $OUT/${TAG}_instruction_rates.txt 2>&1
 (rocm-smi --showclocks --showpower 2>/dev/null | head -30) > $OUT/${TAG}_rocm_smi.txt
-# the driver's own command: one line with the headline and all sub-records
-python bench.py --steps 10 --warmup 2 > $OUT/${TAG}_bench_default.json 2> $RAW/bench_default.err
+# one line with the headline and all sub-records
+python bench.py --full --steps 10 --warmup 2 > $OUT/${TAG}_bench_default.json 2> $RAW/bench_default.err
 cd /tmp && export TMPDIR=/tmp
 # workload tag : bench.py arguments
 declare -A ARGS=( [msm]="--workload msm --log2n 24" [msm_2p21]="--workload msm --log2n 21" [verify]="--workload verify" \
