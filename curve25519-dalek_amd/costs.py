@@ -25,6 +25,8 @@ Formula sources (file:function):
   e_inv_positive                257 S + 23 M                             lizard.h:jacobi_e_inv_positive (8 per decode / inverse)
   Montgomery ladder step        5 M + 4 S + 0.1 M                        montgomery.h:mont_ladder_step (k_x25519, k_mont_mul, k_mont_mul_bits)
   to_edwards                    255 S + 26 M + inversion / 16            montgomery.hip:k_mont_to_edwards_prep + k_ratio_p32 + k_mont_to_edwards
+  group law, elementwise        add / sub 9 M, neg 0, mul_by_cofactor 3 x (4 S + 3 M) + 1 M, eq 4 M   group.hip:k_group_elem, k_group_eq
+  segmented sum                 (K + 7) / K additions per point (K = 8)  group.hip:k_seg_sum (serial fold of K, six scan steps, the carry-in)
 """
 import math
 
@@ -188,6 +190,29 @@ def montgomery_to_edwards():
     return c
 
 
+def group_elem(op="add", compressed=False):
+    """group.hip:k_group_elem / k_group_eq per item: the operation (ge_add 9 M; ge_neg none; mul_by_cofactor two doublings to projective
+    (4 S + 3 M each) and one to extended (4 S + 4 M); ge_eq 4 M), plus per compressed input one decompression (255 S + 22 M) and for a
+    compressed output the batched compression (5 M + 1/16 inversion)"""
+    ops = {"add": {"M": 9, "S": 0}, "neg": {"M": 0, "S": 0}, "mul_by_cofactor": {"M": 10, "S": 12}, "eq": {"M": 4, "S": 0}}
+    inputs = 1 if op in ("neg", "mul_by_cofactor") else 2
+    c = dict(ops[op])
+    if compressed:
+        c = _add(c, _scaled({"M": 22, "S": 255}, inputs))
+        if op != "eq":
+            c = _add(c, {"M": 5, "S": 0}, _scaled(INV, 1.0 / CHUNK))
+    c["what"] = "%s%s" % (op, ", CompressedEdwardsY in and out" if compressed else ", RAW160")
+    return c
+
+
+def segmented_sum(k=8):
+    """group.hip:k_seg_sum per point at level 0: one addition per point in the lane's serial fold, and per lane (k points) six scan steps
+    and the carry-in addition; the piece levels add 2 / (64 k) of that again per level"""
+    c = _scaled({"M": 9, "S": 0}, (k + 7.0) / k)
+    c["what"] = "(K + 7) / K complete additions, K = %d" % k
+    return c
+
+
 def table():
     """Rows for DESIGN.md (python -m curve25519_dalek_amd.costs)."""
     rows = [("fixed base, radix 2^16 tables", fixed_base_wide(16)), ("fixed base, LDS comb", fixed_base_comb()),
@@ -197,7 +222,9 @@ def table():
             ("Ristretto from_uniform_bytes", ristretto_from_uniform()), ("Edwards hash_to_curve (RO)", edwards_hash_to_curve()),
             ("Lizard encode", lizard_encode()), ("Lizard decode (compressed in)", lizard_decode()), ("map_to_curve_inverse", map_to_curve_inverse()),
             ("MontgomeryPoint mul / mul_bits_be 255", montgomery_mul_bits(255)), ("mul_bits_be 512", montgomery_mul_bits(512)),
-            ("MontgomeryPoint::to_edwards", montgomery_to_edwards())]
+            ("MontgomeryPoint::to_edwards", montgomery_to_edwards()),
+            ("group add, RAW160", group_elem("add")), ("group add, compressed", group_elem("add", True)), ("group eq, RAW160", group_elem("eq")),
+            ("segmented sum, per point", segmented_sum())]
     return [(name, round(c["M"], 1), round(c["S"], 1), int(round(mac(c))), c["what"]) for name, c in rows]
 
 

@@ -61,6 +61,7 @@ __global__ void __launch_bounds__(256) k_var_base(const uint8_t *__restrict__ sc
     ge_p3 P;
     bool good = true;
     if (IN_FMT == 0) { u32 w[8]; load8(points, idx, w); good = ge_decompress(P, w); }
+    else if (IN_FMT == 1) { u32 w[8]; load8(points, idx, w); good = ris_decompress(P, w); }
     else P = raw160_load(points, idx);
     if (NEGATE) P = ge_neg(P);
     if (ok) ok[idx] = good ? 1 : 0;
@@ -276,8 +277,10 @@ __global__ void __launch_bounds__(256) k_place_R(const uint8_t *__restrict__ Ren
 }  // namespace c25519
 
 // ---- variable base ------------------------------------------------------------------------------------
-// ct: the scalars are secret (constant-address table scan); false for public scalars (per-signature verification)
-static int32_t var_base_launch(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, bool negate, bool ct, uint32_t *out40, uint8_t *d_ok) {
+// ct: the scalars are secret (constant-address table scan); false for public scalars (per-signature verification).
+// ris: in_fmt C25519_FMT_RISTRETTO is accepted (RistrettoPoint * Scalar; the callers that take Edwards points only keep rejecting it)
+static int32_t var_base_launch(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, bool negate, bool ct, uint32_t *out40, uint8_t *d_ok,
+                               bool ris = false) {
     const unsigned grid = div_up(n, 256);
     const uint64_t stride = (uint64_t)grid * 256;
     int32_t r = ctx_reserve(ctx, ctx->tmp_d, stride * 9 * 160);
@@ -291,6 +294,8 @@ static int32_t var_base_launch(c25519_ctx *ctx, const uint8_t *d_scalars, const 
     } else if (in_fmt == C25519_FMT_RAW160) {
         if (negate) { if (ct) VB(2, true, true); else VB(2, true, false); }
         else { if (ct) VB(2, false, true); else VB(2, false, false); }
+    } else if (in_fmt == C25519_FMT_RISTRETTO && ris && !negate) {
+        if (ct) VB(1, false, true); else VB(1, false, false);
     } else return bad_arg(ctx, "mul_batch: in_fmt must be 0 or 2");
 #undef VB
     HIPCHK(hipGetLastError());
@@ -298,9 +303,27 @@ static int32_t var_base_launch(c25519_ctx *ctx, const uint8_t *d_scalars, const 
     return C25519_OK;
 }
 
-int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok, bool ct) {
+// the Ristretto pairs of the group format rule: in 1 -> out 1 or 2, in 2 -> out 1 (RistrettoPoint * Scalar, ristretto.rs:910-935)
+static bool ris_mul_pair(int in_fmt, int out_fmt) {
+    return (in_fmt == C25519_FMT_RISTRETTO && ris_fmt_ok(out_fmt)) || (in_fmt == C25519_FMT_RAW160 && out_fmt == C25519_FMT_RISTRETTO);
+}
+// P40 results -> compressed Ristretto through a raw staging buffer (scratch, wiped when the scalars were secret)
+static int32_t p40_to_ristretto(c25519_ctx *ctx, const uint32_t *a40, const uint32_t *b40, uint64_t n, uint8_t *d_out, bool wipe_raw, hipStream_t st) {
+    int32_t r;
+    if ((r = ctx_reserve(ctx, ctx->scratch, n * 160))) return r;
+    stream_wipe wipe(st);
+    if (wipe_raw) wipe.add(ctx->scratch.p, n * 160);
+    hipLaunchKernelGGL(k_p40_to_raw, dim3(div_up(n, 256)), dim3(256), 0, st, a40, b40, n, (uint8_t *)ctx->scratch.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(launch_compress_ristretto((const uint8_t *)ctx->scratch.p, n, d_out, st));
+    return C25519_OK;
+}
+// ris: the Ristretto pairs are accepted (c25519_mul_batch); mul_batch_impl, for the Edwards-only callers, keeps rejecting them
+static int32_t mul_batch_core(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok,
+                              bool ct, bool ris) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ed_fmt_ok(out_fmt)) return bad_arg(ctx, "mul_batch: out_fmt must be 0 or 2");
+    const bool rp = ris && ris_mul_pair(in_fmt, out_fmt);
+    if (!ed_fmt_ok(out_fmt) && !rp) return bad_arg(ctx, "mul_batch: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_e, n * 160 + n + 256))) return r;
@@ -309,10 +332,12 @@ int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
     hipEvent_t *ring = ctx_ring_item(ctx);
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     HIPCHK(hipEventRecord(ring[0], ctx->stream));
-    if ((r = var_base_launch(ctx, d_scalars, d_points, n, in_fmt, false, ct, p40, okbuf))) return r;
+    if ((r = var_base_launch(ctx, d_scalars, d_points, n, in_fmt, false, ct, p40, okbuf, rp))) return r;
     HIPCHK(hipEventRecord(ring[1], ctx->stream));
     if (out_fmt == C25519_FMT_RAW160) {
         hipLaunchKernelGGL(k_p40_to_raw, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, p40, (const uint32_t *)nullptr, n, d_out);
+    } else if (out_fmt == C25519_FMT_RISTRETTO) {
+        if ((r = p40_to_ristretto(ctx, p40, nullptr, n, d_out, ct, ctx->stream))) return r;
     } else {
         if ((r = ctx_reserve(ctx, ctx->scratch, n * 128)) || (r = ctx_reserve(ctx, ctx->prefix, n * 48))) return r;
         stream_wipe wipe(ctx->stream);                    // (declared before the launches: also wiped if one of them fails)
@@ -325,8 +350,11 @@ int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return C25519_OK;
 }
+int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok, bool ct) {
+    return mul_batch_core(ctx, d_scalars, d_points, n, in_fmt, out_fmt, d_out, d_ok, ct, false);
+}
 EXPORT int32_t c25519_mul_batch_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok) {
-    return mul_batch_impl(ctx, d_scalars, d_points, n, in_fmt, out_fmt, d_out, d_ok, !(ctx->flags & C25519_FLAG_VARTIME_TABLES));
+    return mul_batch_core(ctx, d_scalars, d_points, n, in_fmt, out_fmt, d_out, d_ok, !(ctx->flags & C25519_FLAG_VARTIME_TABLES), true);
 }
 // ---- order checks (edwards.rs:1405-1437) --------------------------------------------------------------------------------------
 namespace c25519 {
@@ -395,7 +423,7 @@ static int32_t mul_batch_host(c25519_ctx *ctx, const uint8_t *scalars, const uin
     return ffi_twin(ctx, n, 1u << 16, {{scalars, 32, FFI_TMP_A, 16, secret}, {points, point_bytes(in_fmt), FFI_TMP_B, 16}},
                     {{out, point_bytes(out_fmt), FFI_TMP_C, 16, secret}, {ok, 1, FFI_TMP_C}}, [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) -> int32_t {
                         if (clamp) HIPCHK(launch_clamp(d_in[0], m, d_in[0], ctx->stream));
-                        return mul_batch_impl(ctx, d_in[0], d_in[1], m, in_fmt, out_fmt, d_out[0], d_out[1], secret);
+                        return mul_batch_core(ctx, d_in[0], d_in[1], m, in_fmt, out_fmt, d_out[0], d_out[1], secret, !clamp);
                     });
 }
 EXPORT int32_t c25519_mul_batch(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, int out_fmt, uint8_t *out, uint8_t *ok) {
@@ -419,7 +447,8 @@ EXPORT int32_t c25519_mul_clamped_batch(c25519_ctx *ctx, const uint8_t *bytes, c
 EXPORT int32_t c25519_double_base_batch_dev(c25519_ctx *ctx, const uint8_t *d_a, const uint8_t *d_A, const uint8_t *d_b, uint64_t n, int in_fmt, int out_fmt,
                                             uint8_t *d_out, uint8_t *d_ok) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ed_fmt_ok(out_fmt)) return bad_arg(ctx, "double_base: out_fmt must be 0 or 2");
+    const bool rp = ris_mul_pair(in_fmt, out_fmt);       // RistrettoPoint::vartime_double_scalar_mul_basepoint (ristretto.rs:1054)
+    if (!ed_fmt_ok(out_fmt) && !rp) return bad_arg(ctx, "double_base: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_e, 2 * n * 160 + n + 256))) return r;
@@ -429,11 +458,13 @@ EXPORT int32_t c25519_double_base_batch_dev(c25519_ctx *ctx, const uint8_t *d_a,
     hipEvent_t *ring = ctx_ring_item(ctx);
     HIPCHK(hipEventRecord(ctx->ev0, st));
     HIPCHK(hipEventRecord(ring[0], st));
-    if ((r = var_base_launch(ctx, d_a, d_A, n, in_fmt, false, false, P40, okbuf))) return r;          // a * A (vartime by contract)
+    if ((r = var_base_launch(ctx, d_a, d_A, n, in_fmt, false, false, P40, okbuf, rp))) return r;      // a * A (vartime by contract)
     HIPCHK(hipEventRecord(ring[1], st));
     HIPCHK(launch_mul_base_p40(ctx->w, d_b, n, ctx->d_table, Q40, ctx->num_cus, st));                 // b * B (public)
     if (out_fmt == C25519_FMT_RAW160) {
         hipLaunchKernelGGL(k_p40_to_raw, dim3(div_up(n, 256)), dim3(256), 0, st, P40, Q40, n, d_out);
+    } else if (out_fmt == C25519_FMT_RISTRETTO) {
+        if ((r = p40_to_ristretto(ctx, P40, Q40, n, d_out, false, st))) return r;
     } else {
         if ((r = ctx_reserve(ctx, ctx->scratch, n * 128)) || (r = ctx_reserve(ctx, ctx->prefix, n * 48))) return r;
         hipLaunchKernelGGL(k_p40_add_to_p32, dim3(div_up(n, 256)), dim3(256), 0, st, P40, Q40, n, (uint32_t *)ctx->scratch.p);

@@ -25,6 +25,9 @@ error behaviour), batched, on top of Engine.  Reference entry points mirrored:
   MontgomeryPoint::mul (Mul<&Scalar>) / mul_bits_be / mul_base / to_edwards / mul_clamped / mul_base_clamped
                                               curve25519-dalek/src/montgomery.rs:484 / :183 / :144 / :239 / :150 / :166
   EdwardsPoint::is_small_order / is_torsion_free   curve25519-dalek/src/edwards.rs:1405 / :1435;  VerifyingKey::is_weak  ed25519-dalek/src/verifying.rs:192
+  EdwardsPoint / RistrettoPoint Add, Sub, Neg, ConstantTimeEq, is_identity, Sum (add, sub, neg, ct_eq, is_identity, sum, sum_segments),
+  EdwardsPoint::mul_by_cofactor, Mul<&Scalar>    edwards.rs:501 / :808-875 / :1365 / :890, ristretto.rs:815 / :852-907 / :910
+  RistrettoPoint::vartime_double_scalar_mul_basepoint   curve25519-dalek/src/ristretto.rs:1054
 
 Values cross this layer as the reference's wire types: Scalar = 32 canonical LE bytes,
 CompressedEdwardsY / CompressedRistretto / MontgomeryPoint = 32 bytes.
@@ -124,6 +127,48 @@ class EdwardsPoint:
         eng = engine or default_engine()
         out, ok = eng.mul_clamped_batch(_cat(raw_bytes, 32), _cat(points, 32), _e.FMT_EDWARDS_Y, _e.FMT_EDWARDS_Y)
         return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+    # the group law (edwards.rs:501-520, :808-875, :1365, :1484) and EdwardsPoint * Scalar (edwards.rs:890-911): CompressedEdwardsY bytes
+    # in and out (ZIP-215 decoding), None where an input does not decode
+    @staticmethod
+    def add(ps, qs, engine=None):
+        return _group_add(ps, qs, _e.POINT_ADD, _e.FMT_EDWARDS_Y, "add", engine)
+
+    @staticmethod
+    def sub(ps, qs, engine=None):
+        return _group_add(ps, qs, _e.POINT_SUB, _e.FMT_EDWARDS_Y, "sub", engine)
+
+    @staticmethod
+    def neg(ps, engine=None):
+        return _group_map(ps, _e.POINT_NEG, _e.FMT_EDWARDS_Y, engine)
+
+    @staticmethod
+    def mul_by_cofactor(ps, engine=None):
+        return _group_map(ps, _e.POINT_MUL_BY_COFACTOR, _e.FMT_EDWARDS_Y, engine)
+
+    @staticmethod
+    def ct_eq(ps, qs, engine=None):
+        """[P_i == Q_i] (ConstantTimeEq, edwards.rs:501-512: projective equality of the decoded points); None where one does not decode"""
+        return _group_eq(ps, qs, _e.FMT_EDWARDS_Y, "ct_eq", engine)
+
+    @staticmethod
+    def is_identity(ps, engine=None):
+        return _group_eq(ps, None, _e.FMT_EDWARDS_Y, "is_identity", engine)
+
+    @staticmethod
+    def sum(ps, engine=None):
+        """sum of one list (impl Sum, edwards.rs:837-851); the identity for an empty list, None if a point does not decode"""
+        return _group_sum_segments(ps, [len(ps)], _e.FMT_EDWARDS_Y, engine)[0]
+
+    @staticmethod
+    def sum_segments(ps, lengths, engine=None):
+        """[sum of the next lengths[s] points of ps] for every s: many independent sums in one call"""
+        return _group_sum_segments(ps, lengths, _e.FMT_EDWARDS_Y, engine)
+
+    @staticmethod
+    def mul(points, scalars, engine=None):
+        """[P_i * s_i] (edwards.rs:890-911), constant-time unless the engine was made with FLAG_VARTIME_TABLES"""
+        return _group_mul(points, scalars, _e.FMT_EDWARDS_Y, engine)
 
     @staticmethod
     def hash_to_curve(messages, domain_sep, engine=None):
@@ -258,6 +303,94 @@ class RistrettoPoint:
             if b[0] & 0x01 or b[31] & 0xC0:
                 raise ValueError("map_to_curve_restricted: input %d has the bottom bit or one of the top two bits set" % i)
         return RistrettoPoint.map_to_curve(inputs, engine=engine)
+
+    # the group law and scalar multiplication (ristretto.rs:809-935, :1054, :1197): CompressedRistretto bytes in and out, None where an
+    # input does not decode
+    @staticmethod
+    def add(ps, qs, engine=None):
+        return _group_add(ps, qs, _e.POINT_ADD, _e.FMT_RISTRETTO, "add", engine)
+
+    @staticmethod
+    def sub(ps, qs, engine=None):
+        return _group_add(ps, qs, _e.POINT_SUB, _e.FMT_RISTRETTO, "sub", engine)
+
+    @staticmethod
+    def neg(ps, engine=None):
+        return _group_map(ps, _e.POINT_NEG, _e.FMT_RISTRETTO, engine)
+
+    @staticmethod
+    def ct_eq(ps, qs, engine=None):
+        """[P_i == Q_i] (ConstantTimeEq, ristretto.rs:815-830: equality of the group elements, not of the bytes); None where one does not decode"""
+        return _group_eq(ps, qs, _e.FMT_RISTRETTO, "ct_eq", engine)
+
+    @staticmethod
+    def is_identity(ps, engine=None):
+        return _group_eq(ps, None, _e.FMT_RISTRETTO, "is_identity", engine)
+
+    @staticmethod
+    def sum(ps, engine=None):
+        """sum of one list (impl Sum, ristretto.rs:882-895); the identity for an empty list, None if a point does not decode"""
+        return _group_sum_segments(ps, [len(ps)], _e.FMT_RISTRETTO, engine)[0]
+
+    @staticmethod
+    def sum_segments(ps, lengths, engine=None):
+        """[sum of the next lengths[s] points of ps] for every s: many independent sums in one call"""
+        return _group_sum_segments(ps, lengths, _e.FMT_RISTRETTO, engine)
+
+    @staticmethod
+    def mul(points, scalars, engine=None):
+        """[P_i * s_i] (RistrettoPoint * Scalar, ristretto.rs:910-935), constant-time unless the engine was made with FLAG_VARTIME_TABLES"""
+        return _group_mul(points, scalars, _e.FMT_RISTRETTO, engine)
+
+    @staticmethod
+    def vartime_double_scalar_mul_basepoint(a, A, b, engine=None):
+        """[a_i * A_i + b_i * B] (ristretto.rs:1054): A_i as CompressedRistretto; None where A_i does not decode"""
+        if not (len(a) == len(A) == len(b)):
+            raise AssertionError("vartime_double_scalar_mul_basepoint: a, A, b must have equal length")
+        eng = engine or default_engine()
+        out, ok = eng.double_base_batch(_cat(a, 32), _cat(A, 32), _cat(b, 32), _e.FMT_RISTRETTO, _e.FMT_RISTRETTO)
+        return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+
+def _group_add(ps, qs, op, fmt, what, engine):
+    if len(ps) != len(qs):
+        raise AssertionError("%s: both lists must have equal length" % what)
+    eng = engine or default_engine()
+    _, out, ok = eng.point_add_batch(_cat(ps, 32), _cat(qs, 32), op, fmt, fmt)
+    return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+
+def _group_map(ps, op, fmt, engine):
+    eng = engine or default_engine()
+    _, out, ok = eng.point_map_batch(_cat(ps, 32), op, fmt, fmt)
+    return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+
+def _group_eq(ps, qs, fmt, what, engine):
+    if qs is not None and len(ps) != len(qs):
+        raise AssertionError("%s: both lists must have equal length" % what)
+    eng = engine or default_engine()
+    _, eq, ok = eng.point_eq_batch(_cat(ps, 32), _cat(qs, 32) if qs is not None else None, fmt, fmt)
+    return [bool(eq[i]) if ok[i] else None for i in range(eq.shape[0])]
+
+
+def _group_sum_segments(ps, lengths, fmt, engine):
+    lengths = [int(x) for x in lengths]
+    if any(x < 0 for x in lengths) or sum(lengths) != len(ps):
+        raise AssertionError("sum_segments: the lengths must be non-negative and add up to the number of points")
+    off = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lengths, dtype=np.uint64)
+    eng = engine or default_engine()
+    _, out, ok = eng.point_sum_segments(_cat(ps, 32), off, fmt, fmt)
+    return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+
+def _group_mul(points, scalars, fmt, engine):
+    if len(points) != len(scalars):
+        raise AssertionError("mul: points and scalars must have equal length")
+    eng = engine or default_engine()
+    out, ok = eng.mul_batch(_cat(scalars, 32), _cat(points, 32), fmt, fmt)
+    return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
 
 
 class MontgomeryPoint:

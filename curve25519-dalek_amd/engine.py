@@ -16,6 +16,8 @@ LIZARD_NONE, LIZARD_OK, LIZARD_BAD_ENCODING = 0, 1, 2      # per-item status of 
 MONTGOMERY_MAX_BITS = 512        # C25519_MONTGOMERY_MAX_BITS: the longest bit string of montgomery_mul_bits_be
 FMT_EDWARDS_Y, FMT_RISTRETTO, FMT_RAW160 = 0, 1, 2
 POINT_DECODES, POINT_SMALL_ORDER, POINT_TORSION_FREE = 1, 2, 4      # flags of c25519_point_order_checks_batch
+POINT_ADD, POINT_SUB = 0, 1                   # c25519_point_add_batch op
+POINT_NEG, POINT_MUL_BY_COFACTOR = 0, 1       # c25519_point_map_batch op
 Z_TRANSCRIPT, Z_DEVICE = 0, 1
 FLAG_VARTIME_TABLES = 0x100      # c25519_ctx_create: fast secret-indexed tables for mul_base / mul_batch / sign / keygen (public scalars only)
 
@@ -151,6 +153,14 @@ _SIGS = {
     "c25519_montgomery_mul_base_batch": (_i32, [_vp, _vp, _u64, _vp]),
     "c25519_montgomery_to_edwards_batch_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_montgomery_to_edwards_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_point_add_batch_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_point_add_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_point_map_batch_dev": (_i32, [_vp, _vp, _u64, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_point_map_batch": (_i32, [_vp, _vp, _u64, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_point_eq_batch_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_point_eq_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
+    "c25519_point_sum_segments_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_point_sum_segments": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_microbench": (C.c_double, [_vp, C.c_int, C.c_int]),
     "c25519_selftest_field": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _u64, _vp]),
     "c25519_selftest_scalar": (_i32, [_vp, C.c_int, _vp, _vp, _u64, _vp]),
@@ -581,6 +591,52 @@ class Engine:
         self._chk(self.lib.c25519_montgomery_to_edwards_batch_dev(self.ctx, u.data_ptr(), signs.data_ptr(), n, out_fmt, out.data_ptr(), st.data_ptr()))
         return out, st
 
+    # -- the group law on device tensors (edwards.rs / ristretto.rs Add, Sub, Neg, mul_by_cofactor, ConstantTimeEq, Sum) -----------
+    # Each returns (status, result, ok): status OK, or NONE when a compressed input does not decode (ok[i] = 0 there).
+    def point_add_batch_t(self, p, q, op=POINT_ADD, in_fmt=FMT_RAW160, out_fmt=FMT_RAW160):
+        """p[i] + q[i] (op POINT_ADD) or p[i] - q[i] (POINT_SUB): (n, 32|160) uint8 tensors -> (status, (n, 32|160), ok (n,))"""
+        n = self._t(p, _PT[in_fmt])
+        assert self._t(q, _PT[in_fmt]) == n
+        out = self.torch.empty((n, _PT.get(out_fmt, 32)), dtype=self.torch.uint8, device=self.device)
+        ok = self.torch.empty((n,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_point_add_batch_dev(self.ctx, p.data_ptr(), q.data_ptr(), n, op, in_fmt, out_fmt, out.data_ptr(), ok.data_ptr()), (OK, NONE))
+        return st, out, ok
+
+    def point_map_batch_t(self, p, op=POINT_NEG, in_fmt=FMT_RAW160, out_fmt=FMT_RAW160):
+        """-p[i] (op POINT_NEG) or [8] p[i] (POINT_MUL_BY_COFACTOR, Edwards only) -> (status, (n, 32|160), ok (n,))"""
+        n = self._t(p, _PT[in_fmt])
+        out = self.torch.empty((n, _PT.get(out_fmt, 32)), dtype=self.torch.uint8, device=self.device)
+        ok = self.torch.empty((n,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_point_map_batch_dev(self.ctx, p.data_ptr(), n, op, in_fmt, out_fmt, out.data_ptr(), ok.data_ptr()), (OK, NONE))
+        return st, out, ok
+
+    def point_eq_batch_t(self, p, q=None, in_fmt=FMT_RAW160, group=FMT_EDWARDS_Y):
+        """p[i] == q[i] in `group` (FMT_EDWARDS_Y or FMT_RISTRETTO), or p[i] == identity with q None -> (status, eq (n,), ok (n,))"""
+        n = self._t(p, _PT[in_fmt])
+        if q is not None:
+            assert self._t(q, _PT[in_fmt]) == n
+        eq = self.torch.empty((n,), dtype=self.torch.uint8, device=self.device)
+        ok = self.torch.empty((n,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_point_eq_batch_dev(self.ctx, p.data_ptr(), q.data_ptr() if q is not None else None, n, in_fmt, group,
+                                                          eq.data_ptr(), ok.data_ptr()), (OK, NONE))
+        return st, eq, ok
+
+    def point_sum_segments_t(self, points, seg_off, in_fmt=FMT_RAW160, out_fmt=FMT_RAW160):
+        """sums of points[seg_off[s] .. seg_off[s+1]): points (n, 32|160) uint8, seg_off (m + 1,) int64 CUDA tensor, trusted (monotone, 0 .. n;
+        it stays on the device) -> (status, (m, 32|160), ok (m,))"""
+        n = self._t(points, _PT[in_fmt])
+        assert seg_off.is_cuda and seg_off.dtype in (self.torch.int64, self.torch.uint64) and seg_off.is_contiguous() and seg_off.numel() >= 1
+        m = seg_off.numel() - 1
+        out = self.torch.empty((m, _PT.get(out_fmt, 32)), dtype=self.torch.uint8, device=self.device)
+        ok = self.torch.empty((m,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_point_sum_segments_dev(self.ctx, points.data_ptr(), n, in_fmt, seg_off.data_ptr(), m, out_fmt,
+                                                              out.data_ptr(), ok.data_ptr()), (OK, NONE))
+        return st, out, ok
+
     # -- host-buffer API (numpy in / numpy out) ---------------------------------------------------
     @staticmethod
     def _out(out, n, width):
@@ -990,6 +1046,49 @@ class Engine:
         self._bind_stream()
         self._chk(self.lib.c25519_montgomery_to_edwards_batch(self.ctx, u.ctypes.data, sg.ctypes.data, n, out_fmt, out.ctypes.data, st.ctypes.data))
         return out, st
+
+    # -- the group law, host buffers: each returns (status OK | NONE, result numpy, ok numpy (n,) uint8)
+    def point_add_batch(self, p, q, op=POINT_ADD, in_fmt=FMT_RAW160, out_fmt=FMT_RAW160):
+        """p[i] + q[i] (POINT_ADD) or p[i] - q[i] (POINT_SUB) (edwards.rs:808-835, ristretto.rs:852-880)"""
+        a = _np8(p, _PT.get(in_fmt, 32)); b = _np8(q, _PT.get(in_fmt, 32)); n = a.shape[0]
+        assert b.shape[0] == n
+        out = np.empty((n, _PT.get(out_fmt, 32)), np.uint8); ok = np.empty((n,), np.uint8)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_point_add_batch(self.ctx, a.ctypes.data, b.ctypes.data, n, op, in_fmt, out_fmt, out.ctypes.data, ok.ctypes.data), (OK, NONE))
+        return st, out, ok
+
+    def point_map_batch(self, p, op=POINT_NEG, in_fmt=FMT_RAW160, out_fmt=FMT_RAW160):
+        """-p[i] (POINT_NEG) or [8] p[i] (POINT_MUL_BY_COFACTOR, edwards.rs:1365; Edwards only)"""
+        a = _np8(p, _PT.get(in_fmt, 32)); n = a.shape[0]
+        out = np.empty((n, _PT.get(out_fmt, 32)), np.uint8); ok = np.empty((n,), np.uint8)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_point_map_batch(self.ctx, a.ctypes.data, n, op, in_fmt, out_fmt, out.ctypes.data, ok.ctypes.data), (OK, NONE))
+        return st, out, ok
+
+    def point_eq_batch(self, p, q=None, in_fmt=FMT_RAW160, group=FMT_EDWARDS_Y):
+        """p[i] == q[i] in `group`, or p[i] == identity with q None -> (status, eq (n,), ok (n,))"""
+        a = _np8(p, _PT.get(in_fmt, 32)); n = a.shape[0]
+        b = None
+        if q is not None:
+            b = _np8(q, _PT.get(in_fmt, 32))
+            assert b.shape[0] == n
+        eq = np.empty((n,), np.uint8); ok = np.empty((n,), np.uint8)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_point_eq_batch(self.ctx, a.ctypes.data, b.ctypes.data if b is not None else None, n, in_fmt, group,
+                                                      eq.ctypes.data, ok.ctypes.data), (OK, NONE))
+        return st, eq, ok
+
+    def point_sum_segments(self, points, seg_off, in_fmt=FMT_RAW160, out_fmt=FMT_RAW160):
+        """sums of points[seg_off[s] .. seg_off[s+1]) (impl Sum, edwards.rs:837-851): seg_off m + 1 offsets, checked here -> (status, (m, 32|160), ok (m,))"""
+        a = _np8(points, _PT.get(in_fmt, 32)) if len(points) else np.zeros((0, _PT.get(in_fmt, 32)), np.uint8)
+        off = np.ascontiguousarray(np.asarray(seg_off, dtype=np.uint64).reshape(-1))
+        assert off.shape[0] >= 1
+        m = off.shape[0] - 1
+        out = np.empty((m, _PT.get(out_fmt, 32)), np.uint8); ok = np.empty((m,), np.uint8)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_point_sum_segments(self.ctx, a.ctypes.data, a.shape[0], in_fmt, off.ctypes.data, m, out_fmt, out.ctypes.data,
+                                                          ok.ctypes.data), (OK, NONE))
+        return st, out, ok
 
     def scalar_invert_batch(self, scalars):
         """-> (inverses (n,32), product of all inverses (32 bytes)); inputs must be canonical and non-zero."""

@@ -340,7 +340,9 @@ int32_t c25519_debug_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n,
  * replaces backend::variable_base_mul (backend.rs:253 -> scalar_mul/variable_base.rs:11-47;
  * `&EdwardsPoint * &Scalar`, edwards.rs:890-911), radix-16 fixed windows, one pair per lane.
  * points: n x 32 (fmt 0) or n x 160 (fmt 2); out: n x 32 (fmt 0) or n x 160 (fmt 2);
- * ok (may be NULL): n bytes, 0 where a compressed point did not decode (that output is unspecified). */
+ * ok (may be NULL): n bytes, 0 where a compressed point did not decode (that output is unspecified).
+ * RistrettoPoint * Scalar (ristretto.rs:910-935): in_fmt C25519_FMT_RISTRETTO with out_fmt 1 or 2, or in_fmt 2 with out_fmt 1 (the
+ * same ladder; Ristretto decoding and compression).  c25519_mul_clamped_batch stays Edwards only. */
 int32_t c25519_mul_batch_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok);
 int32_t c25519_mul_batch(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, int out_fmt, uint8_t *out, uint8_t *ok);
 
@@ -364,7 +366,8 @@ int32_t c25519_point_order_checks_batch(c25519_ctx *ctx, const uint8_t *points, 
 /* ---- double base: out[i] = a[i] * A[i] + b[i] * B ---------------------------------------------------------
  * replaces backend::vartime_double_base_mul (backend.rs:267 -> scalar_mul/vartime_double_base.rs:23-72;
  * EdwardsPoint::vartime_double_scalar_mul_basepoint, edwards.rs:1099-1106), the single-signature kernel,
- * batched: a radix-16 ladder on A_i plus the fixed-base table on B.  Formats and `ok` as c25519_mul_batch. */
+ * batched: a radix-16 ladder on A_i plus the fixed-base table on B.  Formats and `ok` as c25519_mul_batch, the Ristretto pairs included:
+ * RistrettoPoint::vartime_double_scalar_mul_basepoint (ristretto.rs:1054). */
 int32_t c25519_double_base_batch_dev(c25519_ctx *ctx, const uint8_t *d_a, const uint8_t *d_A, const uint8_t *d_b, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok);
 int32_t c25519_double_base_batch(c25519_ctx *ctx, const uint8_t *a, const uint8_t *A, const uint8_t *b, uint64_t n, int in_fmt, int out_fmt, uint8_t *out, uint8_t *ok);
 
@@ -511,6 +514,42 @@ int32_t c25519_montgomery_mul_base_batch(c25519_ctx *ctx, const uint8_t *scalars
 int32_t c25519_montgomery_to_edwards_batch_dev(c25519_ctx *ctx, const uint8_t *d_u, const uint8_t *d_signs, uint64_t n, int out_fmt, uint8_t *d_out,
                                                uint8_t *d_status);
 int32_t c25519_montgomery_to_edwards_batch(c25519_ctx *ctx, const uint8_t *u, const uint8_t *signs, uint64_t n, int out_fmt, uint8_t *out, uint8_t *status);
+
+/* ---- the group law: add, sub, neg, mul_by_cofactor, eq / is_identity and segmented sums, one group per call --------------------
+ * Formats: in_fmt / out_fmt must belong to one group -- in C25519_FMT_EDWARDS_Y -> out 0 or 2, in C25519_FMT_RISTRETTO -> out 1 or 2,
+ * in C25519_FMT_RAW160 -> out 0, 1 or 2 (the group is the output's; RAW160 -> RAW160 is the same arithmetic in both groups).  Any
+ * other pair returns -(hipErrorInvalidValue).  Compressed inputs are decoded as CompressedEdwardsY::decompress (ZIP-215) or
+ * CompressedRistretto::decompress; a RAW160 input is trusted to be a point.  ok (may be NULL) is 1 where every input of the item decodes
+ * (its output is unspecified otherwise), and the call returns C25519_NONE if any item fails to decode, as c25519_decompress_batch
+ * does: the _dev forms with a compressed input synchronise the context's stream to read that verdict; with RAW160 input they do not.
+ * n == 0 returns C25519_OK.  No branch and no address depends on point data. */
+#define C25519_POINT_ADD 0
+#define C25519_POINT_SUB 1
+/* impl Add / Sub for EdwardsPoint (edwards.rs:808-835) and RistrettoPoint (ristretto.rs:852-880): out[i] = p[i] + q[i] (op
+ * C25519_POINT_ADD) or p[i] - q[i] (C25519_POINT_SUB); p, q, out: n points each. */
+int32_t c25519_point_add_batch_dev(c25519_ctx *ctx, const uint8_t *d_p, const uint8_t *d_q, uint64_t n, int op, int in_fmt, int out_fmt, uint8_t *d_out,
+                                   uint8_t *d_ok);
+int32_t c25519_point_add_batch(c25519_ctx *ctx, const uint8_t *p, const uint8_t *q, uint64_t n, int op, int in_fmt, int out_fmt, uint8_t *out, uint8_t *ok);
+#define C25519_POINT_NEG 0
+#define C25519_POINT_MUL_BY_COFACTOR 1      /* Edwards only: rejected when either format is C25519_FMT_RISTRETTO */
+/* impl Neg (edwards.rs:853-875, ristretto.rs:897-907) and EdwardsPoint::mul_by_cofactor (edwards.rs:1365): out[i] = -p[i] or [8] p[i]. */
+int32_t c25519_point_map_batch_dev(c25519_ctx *ctx, const uint8_t *d_p, uint64_t n, int op, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok);
+int32_t c25519_point_map_batch(c25519_ctx *ctx, const uint8_t *p, uint64_t n, int op, int in_fmt, int out_fmt, uint8_t *out, uint8_t *ok);
+/* eq[i] = 1 iff p[i] == q[i] in `group` (C25519_FMT_EDWARDS_Y: projective equality, ConstantTimeEq edwards.rs:501-512;
+ * C25519_FMT_RISTRETTO: X1*Y2 == Y1*X2 || X1*X2 == Y1*Y2, ristretto.rs:815-830).  q == NULL compares with the identity
+ * (is_identity, traits.rs:45 / ristretto.rs:1197).  A compressed in_fmt must equal group; RAW160 takes either group.  Points are compared
+ * decoded, never as bytes; eq[i] = 0 where ok[i] = 0. */
+int32_t c25519_point_eq_batch_dev(c25519_ctx *ctx, const uint8_t *d_p, const uint8_t *d_q, uint64_t n, int in_fmt, int group, uint8_t *d_eq, uint8_t *d_ok);
+int32_t c25519_point_eq_batch(c25519_ctx *ctx, const uint8_t *p, const uint8_t *q, uint64_t n, int in_fmt, int group, uint8_t *eq, uint8_t *ok);
+/* sums[s] = sum of points[seg_off[s] .. seg_off[s+1]) for s < m (impl Sum, edwards.rs:837-851, ristretto.rs:882-895).  seg_off: m + 1
+ * non-decreasing u64 with seg_off[0] = 0 and seg_off[m] = n; an empty segment sums to the identity; ok[s] = 0 if a point of segment s
+ * does not decode.  m must be below 2^32 - 1; m == 0 returns C25519_OK.  The host form checks the offsets (-(hipErrorInvalidValue)
+ * otherwise); the _dev form takes d_seg_off on the device and TRUSTS it (it never copies the offsets to the host): offsets that break
+ * the rule give unspecified sums, but no access outside the arrays.  Control flow depends on the offsets only. */
+int32_t c25519_point_sum_segments_dev(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n, int in_fmt, const uint64_t *d_seg_off, uint64_t m, int out_fmt,
+                                      uint8_t *d_sums, uint8_t *d_ok);
+int32_t c25519_point_sum_segments(c25519_ctx *ctx, const uint8_t *points, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m, int out_fmt,
+                                  uint8_t *sums, uint8_t *ok);
 
 /* ---- Scalar::invert_batch_alloc (scalar.rs:802-856): io[i] <- 1/io[i] mod l in place (HOST pointer; all inputs
  * must be canonical and non-zero, as in the reference); prod_inv (32 bytes, may be NULL) receives the product of
