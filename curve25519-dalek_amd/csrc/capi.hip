@@ -180,7 +180,7 @@ static bool ctx_make_streams(c25519_ctx *ctx) {
     hipEventCreateWithFlags(&ctx->ev_lists[0], hipEventDisableTiming); hipEventCreateWithFlags(&ctx->ev_lists[1], hipEventDisableTiming);
     for (int i = 0; i < c25519_ctx::RING; i++) for (int j = 0; j < c25519_ctx::RING_EV; j++) hipEventCreate(&ctx->ring[i][j]);
     // C25519_MAX_SLOTS pass slots + the context's own record (msm.hip drec)
-    if (hipMalloc((void **)&ctx->d_slots, (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32 * 4) != hipSuccess) return false;
+    if (hipMalloc((void **)&ctx->d_slots, C25519_SLOTS_BYTES) != hipSuccess) return false;
     // (coherent + mapped: the publishing kernel writes the slots and the "published" word straight into this buffer while the host polls it)
     if (hipHostMalloc(&ctx->h_msm, (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32 * 4 + 256, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) return false;
     memset((uint8_t *)ctx->h_msm + (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32 * 4, 0, 256);
@@ -194,7 +194,7 @@ c25519_ctx *ctx_peer(c25519_ctx *ctx) {
     c25519_ctx *p = new c25519_ctx();
     p->device = ctx->device; p->flags = ctx->flags; p->num_cus = ctx->num_cus; p->w = ctx->w;
     p->d_table = ctx->d_table; p->d_table_ct = ctx->d_table_ct; p->owns_table = false;
-    if (!ctx_make_streams(p) || hipMalloc(&p->d_flag, 256) != hipSuccess || hipMemset(p->d_flag, 0, 256) != hipSuccess) { c25519_ctx_destroy(p); return nullptr; }
+    if (!ctx_make_streams(p) || hipMalloc(&p->d_flag, C25519_FLAG_BYTES) != hipSuccess || hipMemset(p->d_flag, 0, C25519_FLAG_BYTES) != hipSuccess) { c25519_ctx_destroy(p); return nullptr; }
     ctx->peer = p;
     return p;
 }
@@ -223,7 +223,7 @@ EXPORT c25519_ctx *c25519_ctx_create(int device, uint32_t flags) {
     if (ctx->w == 9) build_comb_table(tab); else build_window_table(ge_basepoint(), ctx->w, tab);
     if (hipMalloc(&ctx->d_table, tab.size() * 4) != hipSuccess ||
         hipMemcpy(ctx->d_table, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&ctx->d_flag, 256) != hipSuccess || hipMemset(ctx->d_flag, 0, 256) != hipSuccess) {
+        hipMalloc(&ctx->d_flag, C25519_FLAG_BYTES) != hipSuccess || hipMemset(ctx->d_flag, 0, C25519_FLAG_BYTES) != hipSuccess) {
         fprintf(stderr, "c25519_ctx_create: device allocation failed\n");
         c25519_ctx_destroy(ctx);
         return nullptr;
@@ -249,8 +249,7 @@ EXPORT void c25519_ctx_destroy(c25519_ctx *ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    devbuf *bufs[] = {&ctx->scratch, &ctx->prefix, &ctx->tmp_a, &ctx->tmp_b, &ctx->tmp_c, &ctx->tmp_c2, &ctx->tmp_d, &ctx->tmp_e, &ctx->tmp_f, &ctx->pts_all, &ctx->dom};
-    for (devbuf *b : bufs) if (b->p) hipFree(b->p);
+    for (const ctx_workspace &w : ctx_workspaces(ctx)) if (w.buf && w.buf->p) hipFree(w.buf->p);      // (the fixed allocations: below)
     if (ctx->peer) { c25519_ctx_destroy(ctx->peer); ctx->peer = nullptr; }
     if (ctx->d_table && ctx->owns_table) hipFree(ctx->d_table);
     if (ctx->d_table_ct && ctx->owns_table) hipFree(ctx->d_table_ct);
@@ -452,8 +451,7 @@ EXPORT int32_t c25519_ctx_trim(c25519_ctx *ctx) {
     for (c25519_ctx *c = ctx; c; c = c->peer) {
         if (c != ctx && c->stream) HIPCHK(hipStreamSynchronize(c->stream));
         if (c->aux) HIPCHK(hipStreamSynchronize(c->aux));
-        devbuf *bufs[] = {&c->scratch, &c->prefix, &c->tmp_a, &c->tmp_b, &c->tmp_c, &c->tmp_c2, &c->tmp_d, &c->tmp_e, &c->tmp_f, &c->pts_all, &c->dom};
-        for (devbuf *b : bufs) if (b->p) { HIPCHK(hipFree(b->p)); b->p = nullptr; b->cap = 0; }
+        for (const ctx_workspace &w : ctx_workspaces(c)) if (w.buf && w.buf->p) { HIPCHK(hipFree(w.buf->p)); w.buf->p = nullptr; w.buf->cap = 0; }
     }
     return C25519_OK;
 }

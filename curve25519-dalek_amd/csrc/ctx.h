@@ -78,6 +78,21 @@ struct c25519_ctx {
     std::string err;
 };
 
+// Every device workspace of ONE context (not of its peer), by name: the growable buffers (buf != nullptr) and the two fixed allocations.  The only
+// list of them: c25519_ctx_trim and c25519_ctx_destroy free what it names, the c25519_debug_workspace_* window (diag.hip) reads and zeroes it, so a
+// buffer added to the struct and to this list is covered by tests/test_gpu_wipe.py -- and one left out of it is never freed.
+constexpr size_t C25519_FLAG_BYTES = 256, C25519_SLOTS_BYTES = (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32 * 4;
+struct ctx_workspace { const char *name; devbuf *buf; void *p; size_t cap; };
+inline std::vector<ctx_workspace> ctx_workspaces(c25519_ctx *c) {
+    std::vector<ctx_workspace> v;
+    auto add = [&](const char *name, devbuf &b) { v.push_back({name, &b, b.p, b.cap}); };
+    add("scratch", c->scratch); add("prefix", c->prefix); add("tmp_a", c->tmp_a); add("tmp_b", c->tmp_b); add("tmp_c", c->tmp_c); add("tmp_c2", c->tmp_c2);
+    add("tmp_d", c->tmp_d); add("tmp_e", c->tmp_e); add("tmp_f", c->tmp_f); add("dom", c->dom); add("pts_all", c->pts_all);
+    v.push_back({"d_flag", nullptr, c->d_flag, c->d_flag ? C25519_FLAG_BYTES : 0});
+    v.push_back({"d_slots", nullptr, c->d_slots, c->d_slots ? C25519_SLOTS_BYTES : 0});
+    return v;
+}
+
 // Zeroes device buffers on the given stream when it goes out of scope: secret-derived scratch is wiped on EVERY exit path of an
 // entry point (also the early returns of a failed launch), after whatever the entry point enqueued before.
 struct stream_wipe {
@@ -99,7 +114,13 @@ c25519_ctx *ctx_peer(c25519_ctx *ctx);      // nullptr if it cannot be created
 // fast tables (the radix-2^16 HBM tables by default), whose addresses depend on the scalar.
 // table_ct (may be null = the context's basepoint table): a caller's constant-time window table (c25519_basetable)
 int32_t mul_base_impl(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, int out_fmt, uint8_t *d_out, bool secret, const uint32_t *table_ct = nullptr);
-int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok, bool ct);
+// keep_p40: the caller goes on to read the P40 products this call leaves in tmp_e (and the decode flags behind them, when d_ok is null) and wipes them itself;
+// otherwise a constant-time call zeroes them when it is done
+int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok, bool ct,
+                       bool keep_p40 = false);
+// what mul_batch_impl reserves in tmp_e for n items: the P40 products, the decode flags behind them (when the caller passes no d_ok) and slack.  A caller that
+// registers tmp_e for a wipe BEFORE the call (msm_consttime) reserves exactly this, so the call does not reallocate the buffer under the registration
+inline size_t mul_batch_p40_bytes(uint64_t n) { return (size_t)n * 160 + n + 256; }
 // ring entry of a per-item call (events 0..2)
 inline hipEvent_t *ctx_ring_item(c25519_ctx *ctx) { const int idx = (int)(ctx->ncalls++ % c25519_ctx::RING); ctx->ring_kind[idx] = 0; return ctx->ring[idx]; }
 inline bool ctx_secret_default(const c25519_ctx *ctx) { return !(ctx->flags & 0x100u); }   // !C25519_FLAG_VARTIME_TABLES

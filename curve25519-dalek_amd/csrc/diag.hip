@@ -490,3 +490,55 @@ EXPORT int32_t c25519_selftest_scalar(c25519_ctx *ctx, int op, const uint32_t *a
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return C25519_OK;
 }
+
+// ---- a read-only window on the workspaces (tests/test_gpu_wipe.py: what a secret-taking call leaves behind) ------------------------------------------
+// every workspace of the context (ctx.h ctx_workspaces: the one list of them), then the same of its peer, if it has one
+struct debug_ws { const char *name; bool peer; void *p; size_t cap; };
+static std::vector<debug_ws> debug_workspaces(c25519_ctx *ctx) {
+    std::vector<debug_ws> v;
+    c25519_ctx *both[2] = {ctx, ctx->peer};
+    for (c25519_ctx *c : both) if (c)
+        for (const ctx_workspace &w : ctx_workspaces(c)) v.push_back({w.name, c != ctx, w.p, w.p ? w.cap : 0});
+    return v;
+}
+// everything enqueued on the streams of the context and its peer has finished
+static int32_t debug_drain(c25519_ctx *ctx) {
+    HIPCHK(hipSetDevice(ctx->device));
+    c25519_ctx *both[2] = {ctx, ctx->peer};
+    for (c25519_ctx *c : both) if (c) {
+        hipStream_t sts[4] = {c->stream, c->aux, c->s_h2d, c->s_d2h};
+        for (hipStream_t s : sts) if (s) HIPCHK(hipStreamSynchronize(s));
+    }
+    return C25519_OK;
+}
+EXPORT int32_t c25519_debug_workspace_count(c25519_ctx *ctx) { return ctx ? (int32_t)debug_workspaces(ctx).size() : 0; }
+// *name: "tmp_a", "peer.tmp_a", ... (valid until the next call of this function on any context, from any thread: a test window, not a product path); *cap: the bytes allocated (0: not allocated yet)
+EXPORT int32_t c25519_debug_workspace_info(c25519_ctx *ctx, int which, const char **name, uint64_t *cap) {
+    if (!ctx) return -(int32_t)hipErrorInvalidValue;
+    const std::vector<debug_ws> v = debug_workspaces(ctx);
+    if (which < 0 || (size_t)which >= v.size()) return bad_arg(ctx, "debug_workspace_info: no such workspace");
+    static std::string label;
+    label = std::string(v[which].peer ? "peer." : "") + v[which].name;
+    if (name) *name = label.c_str();
+    if (cap) *cap = v[which].cap;
+    return C25519_OK;
+}
+EXPORT int32_t c25519_debug_workspace_read(c25519_ctx *ctx, int which, uint64_t off, uint64_t bytes, uint8_t *out) {
+    if (!ctx || (bytes && !out)) return -(int32_t)hipErrorInvalidValue;
+    const std::vector<debug_ws> v = debug_workspaces(ctx);
+    if (which < 0 || (size_t)which >= v.size()) return bad_arg(ctx, "debug_workspace_read: no such workspace");
+    if (off > v[which].cap || bytes > v[which].cap - off) return bad_arg(ctx, "debug_workspace_read: range outside the workspace");
+    int32_t r = debug_drain(ctx);
+    if (r) return r;
+    if (bytes) HIPCHK(hipMemcpy(out, (const uint8_t *)v[which].p + off, bytes, hipMemcpyDeviceToHost));
+    return C25519_OK;
+}
+// the only write of this window: every workspace zeroed over its whole capacity
+EXPORT int32_t c25519_debug_workspace_zero(c25519_ctx *ctx) {
+    if (!ctx) return -(int32_t)hipErrorInvalidValue;
+    int32_t r = debug_drain(ctx);
+    if (r) return r;
+    for (const debug_ws &w : debug_workspaces(ctx)) if (w.p && w.cap) HIPCHK(hipMemset(w.p, 0, w.cap));
+    HIPCHK(hipDeviceSynchronize());
+    return C25519_OK;
+}

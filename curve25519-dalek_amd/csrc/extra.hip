@@ -229,19 +229,22 @@ EXPORT int32_t c25519_msm_consttime(c25519_ctx *ctx, const uint8_t *scalars, con
     size_t psz = point_bytes(in_fmt);
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * psz + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 160 + n + 256))) return r;
+    const int K = 4;
+    const size_t fold_bytes = (size_t)(n / (64 * K) + 2) * 160 * 2;
+    if ((r = ctx_reserve(ctx, ctx->tmp_e, mul_batch_p40_bytes(n))) || (r = ctx_reserve(ctx, ctx->tmp_f, fold_bytes + 512))) return r;   // (tmp_e: what mul_batch_impl will ask for)
     hipStream_t st = ctx->stream;
+    // the staged secret scalars, the per-term products s_i P_i (raw in tmp_c, P40 records in tmp_e) and the partial sums of the fold: zeroed on every exit
+    // path, after the last kernel and copy enqueued below (the successful path drains the stream before it returns, so the memsets follow completed work)
+    stream_wipe wipe(st);
+    wipe.add(ctx->tmp_a.p, n * 32); wipe.add(ctx->tmp_c.p, n * 160); wipe.add(ctx->tmp_e.p, n * 160 + n); wipe.add(ctx->tmp_f.p, fold_bytes);
     HIPCHK(hipMemcpyAsync(ctx->tmp_a.p, scalars, n * 32, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ctx->tmp_b.p, points, n * psz, hipMemcpyHostToDevice, st));
     uint8_t *d_raw = (uint8_t *)ctx->tmp_c.p, *d_ok = d_raw + n * 160;
     // always the constant-address table scan, whatever the context's flags: that is what this entry point is for
-    r = mul_batch_impl(ctx, (const uint8_t *)ctx->tmp_a.p, (const uint8_t *)ctx->tmp_b.p, n, in_fmt, C25519_FMT_RAW160, d_raw, d_ok, true);
-    hipMemsetAsync(ctx->tmp_a.p, 0, n * 32, st);          // the staged secret scalars, on every path
-    if (r) return r;
-    // c25519_mul_batch_dev left the products as P40 records in tmp_e: fold them
-    const int K = 4;
+    if ((r = mul_batch_impl(ctx, (const uint8_t *)ctx->tmp_a.p, (const uint8_t *)ctx->tmp_b.p, n, in_fmt, C25519_FMT_RAW160, d_raw, d_ok, true, true))) return r;
+    // mul_batch_impl left the products as P40 records in tmp_e (keep_p40): fold them
     uint32_t *cur = (uint32_t *)ctx->tmp_e.p;
     uint64_t m = n;
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, (size_t)(n / (64 * K) + 2) * 160 * 2 + 512))) return r;
     uint32_t *bufA = (uint32_t *)ctx->tmp_f.p, *bufB = bufA + (size_t)(n / (64 * K) + 2) * 40;
     while (m > 64) {
         uint64_t mo = (m + 64 * K - 1) / (64 * K);
@@ -298,6 +301,10 @@ EXPORT int32_t c25519_scalar_invert_batch(c25519_ctx *ctx, uint8_t *io, uint64_t
             const uint64_t T = (uint64_t)grid * 256;
             int32_t r;
             if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * 40 + 64)) || (r = ctx_reserve(ctx, ctx->tmp_c, T * 40 + 64))) return r;
+            // zeroize (scalar.rs:852), on every exit path: the scalars and their inverses (tmp_a), the prefix products (tmp_b) and the per-lane products of
+            // inverses (tmp_c: for n up to the lane count lane t holds 1 / x_t itself).  The successful path drains the stream before the scope ends.
+            stream_wipe wipe(ctx->stream);
+            wipe.add(ctx->tmp_a.p, n * 32); wipe.add(ctx->tmp_b.p, n * 40); wipe.add(ctx->tmp_c.p, T * 40);
             HIPCHK(hipMemcpyAsync(ctx->tmp_a.p, io, n * 32, hipMemcpyHostToDevice, ctx->stream));
             HIPCHK(hipMemsetAsync(ctx->tmp_c.p, 0, T * 40, ctx->stream));
             hipLaunchKernelGGL(k_scalar_invert<CH>, dim3(grid), dim3(256), 0, ctx->stream, (uint8_t *)ctx->tmp_a.p, n, (uint32_t *)ctx->tmp_b.p, (uint32_t *)ctx->tmp_c.p);
@@ -306,8 +313,6 @@ EXPORT int32_t c25519_scalar_invert_batch(c25519_ctx *ctx, uint8_t *io, uint64_t
             HIPCHK(hipMemcpyAsync(io, ctx->tmp_a.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(parts.data(), ctx->tmp_c.p, T * 40, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
-            HIPCHK(hipMemsetAsync(ctx->tmp_a.p, 0, n * 32, ctx->stream));   // zeroize (scalar.rs:852)
-            HIPCHK(hipMemsetAsync(ctx->tmp_b.p, 0, n * 40, ctx->stream));
             const uint64_t active = n < T ? n : T;     // lane t owns elements t, t+T, ...: every lane below n is active
             for (uint64_t t = 0; t < active; t++) {    // the product over the lanes, on the host (5 x 52 Montgomery form, sc_sha.h)
                 sc28 q28;

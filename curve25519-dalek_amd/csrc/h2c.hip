@@ -120,7 +120,7 @@ static int32_t ris_fixed_host(c25519_ctx *ctx, const uint8_t *in, size_t in_byte
     HIPCHK(hipSetDevice(ctx->device));
     if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, what);
     if (n == 0) return C25519_OK;
-    return ffi_twin(ctx, n, 1u << 16, {{in, in_bytes, FFI_TMP_A}}, {{out, point_bytes(out_fmt), FFI_TMP_B}},
+    return ffi_twin(ctx, n, 1u << 16, {{in, in_bytes, FFI_TMP_A, 0, true}}, {{out, point_bytes(out_fmt), FFI_TMP_B, 0, true}},      /* the uniform bytes may be a secret (a blinded value): staged copies wiped */
                     [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return dev(ctx, d_in[0], m, out_fmt, d_out[0]); });
 }
 EXPORT int32_t c25519_ristretto_from_uniform_bytes_batch(c25519_ctx *ctx, const uint8_t *in64, uint64_t n, int out_fmt, uint8_t *out) {

@@ -132,14 +132,14 @@ EXPORT int32_t c25519_ristretto_lizard_encode_sha256_batch(c25519_ctx *ctx, cons
     HIPCHK(hipSetDevice(ctx->device));
     if (!ris_fmt_ok(out_fmt)) return bad_arg(ctx, "ristretto_lizard_encode: out_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
-    return ffi_twin(ctx, n, 1u << 16, {{data16, 16, FFI_TMP_A}}, {{out, point_bytes(out_fmt), FFI_TMP_B}},
+    return ffi_twin(ctx, n, 1u << 16, {{data16, 16, FFI_TMP_A, 0, true}}, {{out, point_bytes(out_fmt), FFI_TMP_B, 0, true}},      /* the payload and the point that carries it: wiped */
                     [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_ristretto_lizard_encode_sha256_batch_dev(ctx, d_in[0], m, out_fmt, d_out[0]); });
 }
 EXPORT int32_t c25519_ristretto_lizard_decode_sha256_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int in_fmt, uint8_t *out16, uint8_t *status) {
     HIPCHK(hipSetDevice(ctx->device));
     if (!ris_fmt_ok(in_fmt)) return bad_arg(ctx, "ristretto_lizard_decode: in_fmt must be 1 or 2");
     if (n == 0) return C25519_OK;
-    return ffi_twin(ctx, n, 1u << 16, {{in, point_bytes(in_fmt), FFI_TMP_A}}, {{out16, 16, FFI_TMP_B}, {status, 1, FFI_TMP_C}},
+    return ffi_twin(ctx, n, 1u << 16, {{in, point_bytes(in_fmt), FFI_TMP_A, 0, true}}, {{out16, 16, FFI_TMP_B, 0, true}, {status, 1, FFI_TMP_C}},
                     [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_ristretto_lizard_decode_sha256_batch_dev(ctx, d_in[0], m, in_fmt, d_out[0], d_out[1]); });
 }
 EXPORT int32_t c25519_ristretto_map_to_curve_inverse_batch(c25519_ctx *ctx, const uint8_t *in, uint64_t n, int in_fmt, uint8_t *out512, uint16_t *mask,

@@ -211,7 +211,7 @@ EXPORT int32_t c25519_montgomery_to_edwards_batch_dev(c25519_ctx *ctx, const uin
 EXPORT int32_t c25519_montgomery_mul_batch(c25519_ctx *ctx, const uint8_t *k, const uint8_t *u, uint64_t n, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n == 0) return C25519_OK;
-    return ffi_twin(ctx, n, 1u << 17, {{k, 32, FFI_TMP_A, 0, true}, {u, 32, FFI_TMP_B}}, {{out, 32, FFI_TMP_C}},
+    return ffi_twin(ctx, n, 1u << 17, {{k, 32, FFI_TMP_A, 0, true}, {u, 32, FFI_TMP_B}}, {{out, 32, FFI_TMP_C, 0, true}},      /* the products are shared secrets: wiped like the scalars */
                     [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_montgomery_mul_batch_dev(ctx, d_in[0], d_in[1], m, d_out[0]); });
 }
 EXPORT int32_t c25519_montgomery_mul_bits_be_batch(c25519_ctx *ctx, const uint8_t *bits, uint32_t nbits, const uint8_t *u, uint64_t n, uint8_t *out) {
@@ -220,7 +220,7 @@ EXPORT int32_t c25519_montgomery_mul_bits_be_batch(c25519_ctx *ctx, const uint8_
     if (n == 0) return C25519_OK;
     const size_t nb = (nbits + 7) / 8;
     // the staged bits are wiped; with nbits = 0 there is nothing to copy
-    return ffi_twin(ctx, n, 1u << 17, {{u, 32, FFI_TMP_B}, {nb ? bits : nullptr, nb, FFI_TMP_A, 16, true}}, {{out, 32, FFI_TMP_C}},
+    return ffi_twin(ctx, n, 1u << 17, {{u, 32, FFI_TMP_B}, {nb ? bits : nullptr, nb, FFI_TMP_A, 16, true}}, {{out, 32, FFI_TMP_C, 0, true}},
                     [&](uint64_t m, uint8_t *const *d_in, uint8_t *const *d_out) { return c25519_montgomery_mul_bits_be_batch_dev(ctx, d_in[1], nbits, d_in[0], m, d_out[0]); });
 }
 EXPORT int32_t c25519_montgomery_mul_base_batch(c25519_ctx *ctx, const uint8_t *scalars, uint64_t n, uint8_t *out) {

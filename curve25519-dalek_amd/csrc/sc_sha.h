@@ -180,17 +180,20 @@ struct sha512_stream {
     u64 total;
     C25519_HD void init() { sha512_init(h); for (int i = 0; i < 16; i++) w[i] = 0; fill = 0; total = 0; }
     C25519_HD void put_be64(u64 v) {   // absorb 8 bytes given as a big-endian word; fill must be 8-aligned
-        // dynamic index into w[]: written as a select chain so w stays in registers
+        // dynamic index into w[]: every word is rewritten through a select, so each access has a compile-time index and w stays in registers
+        // (a chain of `if (i == slot) w[i] = v` is folded back into ONE store at a run-time index: the block -- the signing prefix in it -- then lives
+        //  in the private segment, which nothing can wipe; tests/test_ct_isa_secret_paths.py)
         u32 slot = fill >> 3;
 #pragma unroll
-        for (int i = 0; i < 16; i++) if ((u32)i == slot) w[i] = v;
+        for (int i = 0; i < 16; i++) w[i] = ((u32)i == slot) ? v : w[i];
         fill += 8; total += 8;
         if (fill == 128) { sha512_compress(h, w); fill = 0; }
     }
     C25519_HD void put_byte(u32 b) {
         u32 slot = fill >> 3, sh = 56 - 8 * (fill & 7);
+        const u64 keep = (fill & 7) == 0 ? 0ull : ~0ull, bits = (u64)b << sh;
 #pragma unroll
-        for (int i = 0; i < 16; i++) if ((u32)i == slot) w[i] = ((fill & 7) == 0 ? 0ull : w[i]) | ((u64)b << sh);
+        for (int i = 0; i < 16; i++) w[i] = ((u32)i == slot) ? ((w[i] & keep) | bits) : w[i];
         fill += 1; total += 1;
         if (fill == 128) { sha512_compress(h, w); fill = 0; }
     }

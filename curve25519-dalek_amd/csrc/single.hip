@@ -320,15 +320,17 @@ static int32_t p40_to_ristretto(c25519_ctx *ctx, const uint32_t *a40, const uint
 }
 // ris: the Ristretto pairs are accepted (c25519_mul_batch); mul_batch_impl, for the Edwards-only callers, keeps rejecting them
 static int32_t mul_batch_core(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok,
-                              bool ct, bool ris) {
+                              bool ct, bool ris, bool keep_p40 = false) {
     HIPCHK(hipSetDevice(ctx->device));
     const bool rp = ris && ris_mul_pair(in_fmt, out_fmt);
     if (!ed_fmt_ok(out_fmt) && !rp) return bad_arg(ctx, "mul_batch: out_fmt must be 0 or 2");
     if (n == 0) return C25519_OK;
     int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_e, n * 160 + n + 256))) return r;
+    if ((r = ctx_reserve(ctx, ctx->tmp_e, mul_batch_p40_bytes(n)))) return r;
     uint32_t *p40 = (uint32_t *)ctx->tmp_e.p;
     uint8_t *okbuf = d_ok ? d_ok : (uint8_t *)ctx->tmp_e.p + n * 160;
+    stream_wipe wipe_p40(ctx->stream);                    // the products secret * P as P40 records (declared first: zeroed after everything below, on every exit path)
+    if (ct && !keep_p40) wipe_p40.add(ctx->tmp_e.p, n * 160 + n);
     hipEvent_t *ring = ctx_ring_item(ctx);
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     HIPCHK(hipEventRecord(ring[0], ctx->stream));
@@ -350,8 +352,9 @@ static int32_t mul_batch_core(c25519_ctx *ctx, const uint8_t *d_scalars, const u
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     return C25519_OK;
 }
-int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok, bool ct) {
-    return mul_batch_core(ctx, d_scalars, d_points, n, in_fmt, out_fmt, d_out, d_ok, ct, false);
+int32_t mul_batch_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok, bool ct,
+                       bool keep_p40) {
+    return mul_batch_core(ctx, d_scalars, d_points, n, in_fmt, out_fmt, d_out, d_ok, ct, false, keep_p40);
 }
 EXPORT int32_t c25519_mul_batch_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, int out_fmt, uint8_t *d_out, uint8_t *d_ok) {
     return mul_batch_core(ctx, d_scalars, d_points, n, in_fmt, out_fmt, d_out, d_ok, !(ctx->flags & C25519_FLAG_VARTIME_TABLES), true);

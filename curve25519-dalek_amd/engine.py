@@ -164,6 +164,10 @@ _SIGS = {
     "c25519_microbench": (C.c_double, [_vp, C.c_int, C.c_int]),
     "c25519_selftest_field": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _u64, _vp]),
     "c25519_selftest_scalar": (_i32, [_vp, C.c_int, _vp, _vp, _u64, _vp]),
+    "c25519_debug_workspace_count": (_i32, [_vp]),
+    "c25519_debug_workspace_info": (_i32, [_vp, C.c_int, _vp, _vp]),
+    "c25519_debug_workspace_read": (_i32, [_vp, C.c_int, _u64, _u64, _vp]),
+    "c25519_debug_workspace_zero": (_i32, [_vp]),
     "c25519_msm_geometry": (_i32, [_u64, _vp, _vp, _vp, _vp, _vp]),
 }
 ABI_SYMBOLS = list(_SIGS)
@@ -295,6 +299,22 @@ class Engine:
         self._bind_stream()
         self._chk(self.lib.c25519_selftest_scalar(self.ctx, op, a.ctypes.data, b.ctypes.data if b is not None else None, n, out.ctypes.data))
         return out
+
+    def workspaces(self):
+        """-> {name: bytes} of every device workspace of the context and its peer, read back after all its streams have drained (c25519_debug_workspace_*)"""
+        out = {}
+        for i in range(self.lib.c25519_debug_workspace_count(self.ctx)):
+            name, cap = C.c_char_p(), C.c_uint64(0)
+            self._chk(self.lib.c25519_debug_workspace_info(self.ctx, i, C.byref(name), C.byref(cap)))
+            buf = np.zeros(cap.value, dtype=np.uint8)
+            if cap.value:
+                self._chk(self.lib.c25519_debug_workspace_read(self.ctx, i, 0, cap.value, buf.ctypes.data))
+            out[name.value.decode()] = buf
+        return out
+
+    def workspace_zero(self):
+        """zero every device workspace over its whole capacity (c25519_debug_workspace_zero: the one write of the debug window)"""
+        self._chk(self.lib.c25519_debug_workspace_zero(self.ctx))
 
     def microbench(self, which, iters=2000):
         self._bind_stream()

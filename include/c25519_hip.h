@@ -580,6 +580,15 @@ int32_t c25519_selftest_field(c25519_ctx *ctx, int op, int chain, const uint32_t
  * 5 out[0] = (a < l), the word-wise test behind from_canonical_bytes (scalar.rs:259-263); 6 words -> limbs -> words of a < 2^256;
  * 7 r + k*a as the signer chains them: k = a mod l (16 words), a = b[0..8] (unreduced, < 2^256), r = b[8..16] (canonical). */
 int32_t c25519_selftest_scalar(c25519_ctx *ctx, int op, const uint32_t *a_words, const uint32_t *b_words, uint64_t n, uint8_t *out);
+/* A read-only window on the device workspaces of a context and of its peer context, for tests/test_gpu_wipe.py: what a call on secrets leaves behind.
+ * count: how many there are (every devbuf of the context, its flag words and its result slots; then the same of the peer, if one exists -- the list is
+ * csrc/ctx.h ctx_workspaces, which c25519_ctx_trim and c25519_ctx_destroy share).  info: *name ("tmp_a", "peer.tmp_a", ...; valid until the next info call)
+ * and *cap, the bytes allocated (0: not yet).  read: bytes [off, off + bytes) of workspace `which` into the HOST buffer out, after every stream of the
+ * context and its peer has drained.  zero: the only write -- every workspace set to zero over its whole capacity; synchronises. */
+int32_t c25519_debug_workspace_count(c25519_ctx *ctx);
+int32_t c25519_debug_workspace_info(c25519_ctx *ctx, int which, const char **name, uint64_t *cap);
+int32_t c25519_debug_workspace_read(c25519_ctx *ctx, int which, uint64_t off, uint64_t bytes, uint8_t *out);
+int32_t c25519_debug_workspace_zero(c25519_ctx *ctx);
 /* The window layout the MSM uses for n terms of RAW points (host arithmetic, no GPU needed; encoded inputs of 4096 .. 6143 terms and verify_batch choose widths of
  * their own -- every record carries the width it was made with): window k covers bits
  * [pos[k], pos[k] + wid[k]) of s' = s + addk (addk as 8 little-endian 32-bit words); all windows but the last two are
