@@ -34,7 +34,7 @@ MAC_PER_M = 100
 MAC_PER_S = 55
 INV = {"M": 11, "S": 254}          # fe_invert
 CHUNK = 16                         # points per lane sharing one inversion (Montgomery's trick): compression, ladder output
-PREP_CHUNK = 64                    # the same in the MSM's normaliser (msm.hip:k_prep_raw2<64, 4>)
+PREP_CHUNK = 64                    # the same in the MSM's normaliser (msm.hip:k_prep_raw2<64>)
 
 reference_mac = {"fixed_base": 47100, "x25519": 231000, "msm": 26500, "verify": 57000, "verify_bytes": 74400}
 
@@ -90,7 +90,7 @@ def x25519():
 
 def _reduce_per_bucket():
     """Bucket reduction sum_b (b+1) B_b, priced at its ALGORITHMIC minimum -- the running-sum method of
-    pippenger.rs:146-151, two complete additions (9 M each) per bucket.  msm.hip:k_reduce_a / k_reduce_b issue more
+    pippenger.rs:146-151, two complete additions (9 M each) per bucket.  reduce.hip:k_reduce_a4 / k_reduce_b4 issue more
     (per 8 buckets: 13 serial additions, then 13 additions + 3 doublings of the wave-wide combine, i.e. 3.25 additions
     + 0.375 doublings per bucket) to cut the dependent chain from 2 x 32768 additions to 40; the surplus is overhead,
     not achieved work."""

@@ -1,10 +1,11 @@
-// Tuning knobs of the library (A/B arms, profiling switches, pass-size overrides).
+// Tuning knobs of the library: test and measurement levers (size boundaries, pass sizes, window widths, forced paths, profiling switches).
 #pragma once
 #include <stdlib.h>
 // ---- tuning knobs ------------------------------------------------------------------------------------------------------------
 // The RELEASE library (lib/libc25519hip.so) reads NOTHING from the environment: C25519_KNOB(name, default) is the default, a compile-time
-// constant, and no "C25519_..." string is left in the binary (tests/test_abi_cpu.py asserts it on the built file).  The A/B arms, the profiling
-// switches and the pass-size overrides the tests use to run many small passes exist only in the TUNING build (make tune ->
+// constant, and no "C25519_..." string is left in the binary (tests/test_abi_cpu.py asserts it on the built file).  A knob only changes a number fed to code
+// the release library runs anyway, or forces a path it also takes for other inputs; an arm that was measured and not adopted is deleted, not kept behind a
+// knob (DESIGN.md section 7 lists the retired ones).  The knobs exist only in the TUNING build (make tune ->
 // lib/libc25519hip_tune.so, -DC25519_TUNING: the same sources, every knob read once per process from C25519_<name>); the tests and tools that
 // need a knob point C25519_HIP_LIB (a Python-side variable of engine.py) at that file.
 #ifdef C25519_TUNING

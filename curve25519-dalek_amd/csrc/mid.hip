@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(MID_SORT_THREADS) k_mid_sort(const uint16_t *_
 }
 
 // ---- accumulate ----------------------------------------------------------------------------------------------------------------------------------------------------
-// over-long lists as a launch of their own (raw points: behind k_mid_acc<0> on the same stream; mid_long.h has the work loop)
+// over-long lists as a launch of their own (affine records: beside or behind the bucket pipeline's k_accumulate; mid_long.h has the work loop)
 template <int FMT>
 __global__ void __launch_bounds__(256) k_mid_long(const u32 *__restrict__ recs, const u32 *__restrict__ sorted, u64 n, msm_geom g, u32 *__restrict__ buckets, u32 max_items,
                                                   const mid_item *__restrict__ items, const u32 *__restrict__ counters, u32 *__restrict__ seg_sums, u32 *__restrict__ long_done) {
@@ -294,11 +294,6 @@ __device__ __forceinline__ void mid_acc_body(const u32 *__restrict__ recs, const
     (void)sgn;
     if (mine) p40_store(buckets, gid, acc);
 }
-template <int FMT>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) k_mid_acc(const u32 *__restrict__ recs, const u32 *__restrict__ sorted, const u32 *__restrict__ base, const u32 *__restrict__ perm, u64 count, u64 n,
-                                                 msm_geom g, u32 *__restrict__ buckets) {
-    mid_acc_body<FMT>(recs, sorted, base, perm, count, n, g, buckets, blockIdx.x);
-}
 // (r6, late) ... and with the over-long lists IN the launch: L.blocks blocks in front of the bucket lanes fold them (mid_long.h; the form accum.hip k_accumulate_long gave
 // verify_batch).  This is what lets the cap on a lane's list come down to where it belongs: the accumulation of a mid-size call is not throughput, it is its LONGEST
 // list -- a chain of dependent additions at 3 - 5 us each (2^17 terms: lists of up to 34 entries, 140 us, where the machine needs 100 for all 2.4 M additions; 2^18
@@ -314,70 +309,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
     mid_acc_body<0>(recs, sorted, base, perm, count, n, g, buckets, blockIdx.x - L.blocks);
 }
 
-// (r6, late) The same with the WAVE-COOPERATIVE GATHER of accum.hip k_accumulate, for the sizes where the buckets outnumber the machine's lanes (2^16 terms and up):
-// k_mid_acc<0> at 2^18 terms is 66 % VALU-busy and its waves wait 1.6x as long as they issue (profiles/r06_mid_acc_pmc.txt) -- every lane fetches its own 160-byte
-// record with ten 16-byte loads, 640 cache-line look-ups per addition and wave, and nothing is in flight during the addition (a register prefetch costs the third wave
-// per SIMD: r06_ab_mid_prefetch.txt).  Here the records of addition i + 1 travel by DMA into LDS during addition i: pieces 0 .. 7 of a record by the eight lanes
-// 8j .. 8j + 7 (eight instructions of eight lines each, the layout of k_accumulate: piece c of record r at position (c + r) mod 8 of the record's eight slots), pieces 8
-// and 9 by lane pairs (two instructions of 32 lines), 128 look-ups per addition; every lane reads its own record back (ten ds_read_b128) before the next DMA is issued.
-// 40 KB of LDS per block, three blocks per compute unit, the register budget of k_mid_acc.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) k_mid_acc_coop(const u32 *__restrict__ recs, const u32 *__restrict__ sorted, const u32 *__restrict__ base, const u32 *__restrict__ perm, u64 count, u64 n,
-                                                 msm_geom g, u32 *__restrict__ buckets) {
-    __shared__ uint4 stage[(256 / 64) * MID_REC_Q * 64];
-    typedef __attribute__((address_space(3))) void lds_void;
-    typedef const __attribute__((address_space(1))) void gbl_void;
-    const u64 tid = (u64)blockIdx.x * 256 + threadIdx.x;
-    const bool in_range = tid < count;                     // every lane of a wave keeps loading for the others
-    const u64 gid = in_range ? perm[tid] : 0;
-    const int k = (int)(gid / g.half), b = (int)(gid % g.half);
-    const u32 lo = base[(u64)k * (g.half + 1) + b], hi = base[(u64)k * (g.half + 1) + b + 1];
-    const bool mine = in_range && hi - lo <= g.long_cap;
-    const u32 *list = sorted + (u64)k * n;
-    const u32 lane = threadIdx.x & 63u;
-    uint4 *slot_a = stage + (threadIdx.x >> 6) * (MID_REC_Q * 64), *slot_b = slot_a + 8 * 64;
-    const uint4 *my_a = slot_a + lane * 8, *my_b = slot_b + lane * 2;
-    const u32 sub = lane >> 3, coff = ((lane & 7u) - sub) & 7u;
-    const u32 len = mine ? hi - lo : 0u;
-    u32 wmax = len;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { u32 o = (u32)__shfl_xor((int)wmax, d, 64); wmax = o > wmax ? o : wmax; }
-    ge_p3 acc = ge_identity();
-    u32 e = 0, e1 = 0;                                   // entries of iterations it and it + 1 (a finished lane keeps a valid index)
-    if (len > 0) e = list[lo];
-    if (len > 1) e1 = list[lo + 1];
-#define C25519_MID_COOP_ISSUE(ent)                                                                                              \
-    {                                                                                                                           \
-        _Pragma("unroll") for (int kk = 0; kk < 8; kk++) {                                                                     \
-            const u32 idx = (u32)__shfl((int)(ent), (int)(8 * kk + sub), 64) & 0x7fffffffu;                                     \
-            const uint4 *src = reinterpret_cast<const uint4 *>(recs) + (u64)MID_REC_Q * idx + coff;                             \
-            __builtin_amdgcn_global_load_lds((gbl_void *)src, (lds_void *)(slot_a + kk * 64), 16, 0, 0);                        \
-        }                                                                                                                       \
-        _Pragma("unroll") for (int m = 0; m < 2; m++) {                                                                        \
-            const u32 idx = (u32)__shfl((int)(ent), (int)(32 * m + (lane >> 1)), 64) & 0x7fffffffu;                             \
-            const uint4 *src = reinterpret_cast<const uint4 *>(recs) + (u64)MID_REC_Q * idx + 8 + (lane & 1u);                  \
-            __builtin_amdgcn_global_load_lds((gbl_void *)src, (lds_void *)(slot_b + m * 64), 16, 0, 0);                         \
-        }                                                                                                                       \
-    }
-    if (wmax > 0) C25519_MID_COOP_ISSUE(e)
-#pragma unroll 1
-    for (u32 it = 0; it < wmax; it++) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        mid_rec<0> cur;
-#pragma unroll
-        for (int c = 0; c < 8; c++) cur.q[c] = my_a[(c + lane) & 7u];
-        cur.q[8] = my_b[0]; cur.q[9] = my_b[1];
-        const bool neg = (e >> 31) != 0, active = it < len;
-        const u32 e_next = e1;
-        if (it + 2 < len) e1 = list[lo + it + 2];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (it + 1 < wmax) C25519_MID_COOP_ISSUE(e_next)
-        if (active) acc = cur.add_to(acc, neg);
-        e = e_next;
-    }
-#undef C25519_MID_COOP_ISSUE
-    if (mine) p40_store(buckets, gid, acc);
-}
-
 }  // namespace c25519
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -389,8 +320,7 @@ static uint64_t msm_mid_max_records() { static const uint64_t v = (uint64_t)C255
 bool msm_mid_serves_terms(uint64_t n) { return n > verify_small_max() && n <= msm_mid_max_records(); }      // (verify_batch's prepared records; whatever width the caller is about to choose)
 // (prepared records below msm_small_max() terms: only with a layout that is not the small path's -- verify_batch from verify_small_max() + 1 terms chooses one)
 bool msm_mid_serves(uint64_t n, const msm_geom &g, bool prepared) {
-    return (n > msm_small_max() || (prepared && n > verify_small_max() && g.half > 64)) && n <= (prepared ? msm_mid_max_records() : msm_mid_max()) && g.c >= 8 && g.c <= 16 && g.half >= 64 &&
-           g.ngroups <= 1;
+    return (n > msm_small_max() || (prepared && n > verify_small_max() && g.half > 64)) && n <= (prepared ? msm_mid_max_records() : msm_mid_max()) && g.c >= 8 && g.c <= 16 && g.half >= 64;
 }
 
 // The cap on a bucket lane's list (longer lists go to the waves of the long path).  A lane walks its list as a chain of dependent additions, so the accumulation lasts as
@@ -467,7 +397,7 @@ int32_t msm_mid_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const void *p
     mid_item *items = (mid_item *)(ws + oLI);
     uint32_t *lgids = (uint32_t *)(ws + oLG), *segs = (uint32_t *)(ws + oLS), *blockflags = (uint32_t *)(ws + oBF), *zw = (uint32_t *)(ws + oZ);
     const uint32_t *recs = (const uint32_t *)points;
-    // raw points: up to MID_PROJ_MAX terms the records are PROJECTIVE (no inversion; 8 M additions in k_mid_acc<0>); above, the batched normaliser (msm.hip
+    // raw points: up to MID_PROJ_MAX terms the records are PROJECTIVE (no inversion; 8 M additions in k_mid_acc_long); above, the batched normaliser (msm.hip
     // k_prep_raw2) makes affine records on this stream WHILE the digits and the sort run on the second one, and the accumulation is the bucket pipeline's
     // k_accumulate (7 M mixed additions, wave-cooperative gathers): its 130 us at 2^18 terms hide behind the sort, and the accumulation of 2^18 terms is
     // throughput, not latency
@@ -512,22 +442,10 @@ int32_t msm_mid_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const void *p
         HIPCHK(hipEventRecord(ctx->ev_join, sl));
     }
     if (proj) {
-        ctx->kname[0] = "c25519::k_mid_acc<0> (mid path: one lane per bucket, 8 M additions on projective Niels records)";
-        // from 2^16 terms (A/B knob MID_COOP_MIN of the tuning build; 0 = never) the cooperative gather
-        // (the cooperative gather: measured level with the separate launch, profiles/r06_ab_mid_coop.txt; A/B knob MID_COOP_MIN of the tuning build, 0 = never)
-        static const uint64_t coop_min = (uint64_t)C25519_KNOB_LL("MID_COOP_MIN", 0);
-        static const int raw_fused = C25519_KNOB("MID_RAW_FUSED", 1);      // A/B knob: 0 = k_mid_long behind the accumulation on the same stream
-        if (coop_min && n >= coop_min) {
-            hipLaunchKernelGGL(k_mid_acc_coop, dim3(nacc), dim3(256), 0, st, recs, sorted, base, perm, nb, n, g, buckets);
-            hipLaunchKernelGGL(k_mid_long<0>, dim3(nlong), dim3(256), 0, st, recs, sorted, n, g, buckets, max_items, items, zw, segs, zw + 576);
-        } else if (raw_fused) {
-            ctx->kname[0] = "c25519::k_mid_acc_long (mid path: one lane per bucket, 8 M additions on projective Niels records; over-long lists in front)";
-            const mid_long_args L = {items, zw, segs, zw + 576, max_items, 128u};
-            hipLaunchKernelGGL(k_mid_acc_long, dim3(nacc + L.blocks), dim3(256), 0, st, recs, sorted, base, perm, nb, n, g, buckets, L);
-        } else {
-            hipLaunchKernelGGL(k_mid_acc<0>, dim3(nacc), dim3(256), 0, st, recs, sorted, base, perm, nb, n, g, buckets);
-            hipLaunchKernelGGL(k_mid_long<0>, dim3(nlong), dim3(256), 0, st, recs, sorted, n, g, buckets, max_items, items, zw, segs, zw + 576);
-        }
+        // (measured and not adopted: the over-long lists as a launch of their own behind the accumulation; the cooperative gather, profiles/r06_ab_mid_coop.txt)
+        ctx->kname[0] = "c25519::k_mid_acc_long (mid path: one lane per bucket, 8 M additions on projective Niels records; over-long lists in front)";
+        const mid_long_args L = {items, zw, segs, zw + 576, max_items, 128u};
+        hipLaunchKernelGGL(k_mid_acc_long, dim3(nacc + L.blocks), dim3(256), 0, st, recs, sorted, base, perm, nb, n, g, buckets, L);
     } else if (fused) {
         ctx->kname[0] = launch_accumulate_long(recs, sorted, base, perm, nb, n, g, buckets, items, zw, segs, zw + 576, max_items, 64, st);
     } else {

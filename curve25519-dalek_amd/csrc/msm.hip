@@ -76,32 +76,24 @@ namespace c25519 {
 // the prefix products live in a [step][piece][lane] layout (8 lines per instruction), and the records go out through an
 // LDS transpose (piece c of record r at position (c + r) mod 8: conflict-free both ways) as eight fully coalesced
 // stores: 272 look-ups per point and wave.  The block of step j+1 (j-1 on the way back) is in flight during step j.
-// NT (round 6, A/B knob PREP_NT): the normaliser's STREAMING traffic -- the raw points it reads (twice) and the prefix products it writes and reads back, 2.7 GB per
-// 2^24-term call -- with the non-temporal cache policy, so that it stops competing for the MALL with the 215 MB of gather records a pass's accumulation lives on (the
-// records it WRITES keep the default policy: they are what the accumulation wants resident).  profiles/r06_ab_mall.txt has the measurement.
-typedef unsigned int nt_u32x4 __attribute__((ext_vector_type(4)));
-template <int NT> __device__ __forceinline__ void prep_store16(uint4 *p, const uint4 &v) {
-    if (NT) __builtin_nontemporal_store((nt_u32x4){v.x, v.y, v.z, v.w}, reinterpret_cast<nt_u32x4 *>(p)); else *p = v;
-}
-template <int NT> __device__ __forceinline__ uint4 prep_load16(const uint4 *p) {
-    if (NT) { const nt_u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u32x4 *>(p)); return make_uint4(v.x, v.y, v.z, v.w); }
-    return *p;
-}
+// (Streaming -- non-temporal -- accesses for the raw points and the prefix products, so that they stop competing for the MALL with the gather records: measured and
+// not adopted, profiles/r06_ab_mall.txt.)
 // SPEC (round 6): points that are EXPECTED to be affine -- the decompressed points VerifyingKeys carry (verifying.rs:64-71; c25519_decompress_batch writes Z = 1).
 // A wave first runs ONE pass over its points: reads X, Y, Z, writes the record of (X, Y), notes whether every Z was 1 -- no prefix products, no second read, no
 // inversion: 288 instead of 544 bytes per point -- and returns if they all were; a wave that met another Z goes through the general algorithm below from the start
 // (its records are rewritten).  verify_batch of 2^20 signatures with cached key points: the normalisation of the keys is the head of the main stream's chain, 0.35 of
 // its 1.32 ms (profiles/r06_timeline_verify_blake2b.txt); 0.11 this way.  (As two launches -- this pass, then the general kernel returning at once on a device flag --
 // the second launch still took 60 - 70 us beside k_hram: its 128 blocks of 72 KB LDS wait for room.  profiles/r06_ab_prep_affine.txt)
-template <int CH, int WPB, int NT = 0, int SPEC = 0>        // points per lane, waves per block, streaming accesses, speculative affine pass
-__global__ void __launch_bounds__(64 * WPB) k_prep_raw2(const uint8_t *__restrict__ in, u64 n, u32 *__restrict__ prefix, u32 *__restrict__ pts, u64 dst0) {
+constexpr int PREP_WPB = 4;                                 // waves per block
+template <int CH, int SPEC = 0>                             // points per lane, speculative affine pass
+__global__ void __launch_bounds__(64 * PREP_WPB) k_prep_raw2(const uint8_t *__restrict__ in, u64 n, u32 *__restrict__ prefix, u32 *__restrict__ pts, u64 dst0) {
     C25519_PRIO_SIDE();
-    __shared__ uint4 stage_in[WPB * 640];                    // per wave: 64 points x 160 bytes
-    __shared__ uint4 stage_out[WPB * 512];                   // per wave: 64 records x 128 bytes
+    __shared__ uint4 stage_in[PREP_WPB * 640];                    // per wave: 64 points x 160 bytes
+    __shared__ uint4 stage_out[PREP_WPB * 512];                   // per wave: 64 records x 128 bytes
     typedef __attribute__((address_space(3))) void lds_void;
     typedef const __attribute__((address_space(1))) void gbl_void;
     const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const u64 T = (u64)gridDim.x * (64 * WPB), t = (u64)blockIdx.x * (64 * WPB) + threadIdx.x, w0 = t - lane;
+    const u64 T = (u64)gridDim.x * (64 * PREP_WPB), t = (u64)blockIdx.x * (64 * PREP_WPB) + threadIdx.x, w0 = t - lane;
     if (w0 >= n) return;                                     // the whole wave is out of range
     uint4 *sin = stage_in + wv * 640, *sout = stage_out + wv * 512;
     const uint4 *in4 = reinterpret_cast<const uint4 *>(in);
@@ -114,12 +106,12 @@ __global__ void __launch_bounds__(64 * WPB) k_prep_raw2(const uint8_t *__restric
         const u64 b4 = (w0 + (u64)(j) * T) * 10;                                                                               \
         if (b4 + 639 <= last4) {                                                                                               \
             _Pragma("unroll") for (int i = 0; i < 10; i++)                                                                    \
-                __builtin_amdgcn_global_load_lds((gbl_void *)(in4 + b4 + (u64)(i * 64) + lane), (lds_void *)(sin + i * 64), 16, 0, NT ? 2 : 0); \
+                __builtin_amdgcn_global_load_lds((gbl_void *)(in4 + b4 + (u64)(i * 64) + lane), (lds_void *)(sin + i * 64), 16, 0, 0); \
         } else {                                                                                                               \
             _Pragma("unroll") for (int i = 0; i < 10; i++) {                                                                  \
                 u64 a = b4 + (u64)(i * 64) + lane;                                                                             \
                 a = a > last4 ? last4 : a;                                                                                     \
-                __builtin_amdgcn_global_load_lds((gbl_void *)(in4 + a), (lds_void *)(sin + i * 64), 16, 0, NT ? 2 : 0);        \
+                __builtin_amdgcn_global_load_lds((gbl_void *)(in4 + a), (lds_void *)(sin + i * 64), 16, 0, 0);        \
             }                                                                                                                  \
         }                                                                                                                      \
     }
@@ -172,9 +164,9 @@ __global__ void __launch_bounds__(64 * WPB) k_prep_raw2(const uint8_t *__restric
             const bool in = t + (u64)j * T < n;
             const u64 l[5] = {z0.x | (u64)z0.y << 32, z0.z | (u64)z0.w << 32, z1.x | (u64)z1.y << 32, z1.z | (u64)z1.w << 32, z2.x | (u64)z2.y << 32};
             affine = affine && (!in || ((l[0] == 1) && ((l[1] | l[2] | l[3] | l[4]) == 0)));
-            prep_store16<NT>(&pre4[(j * 3 + 0) * 64], make_uint4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]));
-            prep_store16<NT>(&pre4[(j * 3 + 1) * 64], make_uint4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]));
-            prep_store16<NT>(&pre4[(j * 3 + 2) * 64], make_uint4(acc.v[8], acc.v[9], 0u, 0u));
+            pre4[(j * 3 + 0) * 64] = make_uint4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
+            pre4[(j * 3 + 1) * 64] = make_uint4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]);
+            pre4[(j * 3 + 2) * 64] = make_uint4(acc.v[8], acc.v[9], 0u, 0u);
             acc = fe_select_m(acc, fe_mul(acc, fe_from_limbs51(l)), lane_mask(in));
         }
     }
@@ -182,7 +174,7 @@ __global__ void __launch_bounds__(64 * WPB) k_prep_raw2(const uint8_t *__restric
     if (__ballot(!affine) != 0ull) inv = fe_select_m(inv, fe_invert(acc), lane_mask(!affine));      // (wave-uniform branch, explicit select)
     const u32 sub = lane >> 3, coff = ((lane & 7u) - sub) & 7u;
     uint4 pa = make_uint4(0, 0, 0, 0), pb = pa, pc = pa;     // prefix product of the step about to be unwound
-    if (nj > 0) { pa = prep_load16<NT>(&pre4[((nj - 1) * 3 + 0) * 64]); pb = prep_load16<NT>(&pre4[((nj - 1) * 3 + 1) * 64]); pc = prep_load16<NT>(&pre4[((nj - 1) * 3 + 2) * 64]); }
+    if (nj > 0) { pa = pre4[((nj - 1) * 3 + 0) * 64]; pb = pre4[((nj - 1) * 3 + 1) * 64]; pc = pre4[((nj - 1) * 3 + 2) * 64]; }
     if (nj > 0) C25519_PREP_ISSUE(nj - 1)
 #pragma unroll 1
     for (int j = nj - 1; j >= 0; j--) {
@@ -192,7 +184,7 @@ __global__ void __launch_bounds__(64 * WPB) k_prep_raw2(const uint8_t *__restric
         const uint4 a = pa, b = pb, c = pc;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (j > 0) {
-            pa = prep_load16<NT>(&pre4[((j - 1) * 3 + 0) * 64]); pb = prep_load16<NT>(&pre4[((j - 1) * 3 + 1) * 64]); pc = prep_load16<NT>(&pre4[((j - 1) * 3 + 2) * 64]);
+            pa = pre4[((j - 1) * 3 + 0) * 64]; pb = pre4[((j - 1) * 3 + 1) * 64]; pc = pre4[((j - 1) * 3 + 2) * 64];
             C25519_PREP_ISSUE(j - 1)
         }
         const u64 lx[5] = {x0.x | (u64)x0.y << 32, x0.z | (u64)x0.w << 32, x1.x | (u64)x1.y << 32, x1.z | (u64)x1.w << 32, x2.x | (u64)x2.y << 32};
@@ -292,93 +284,7 @@ __global__ void __launch_bounds__(64) k_long_combine(const u32 *__restrict__ bas
     }
 }
 
-// ================================================================================================
-// bucket reduction: col_k = sum_b (b+1) * B_b   [pippenger.rs:146-151]
-//
-// Round 1 ran an 8-ary hierarchy of running sums: one serial level and four wave-starved "cooperative" levels with
-// 3..12 doublings each -- five launches and a dependent chain of ~62 additions + 30 doublings (0.33 ms at c = 16).
-// Now two launches.  Level A: one WAVE per segment of 512 buckets; every lane folds 8 consecutive buckets serially
-// (S = sum B_j, W = sum j B_j: 13 additions, the work-efficient part), then the 64 lanes combine through shuffles:
-//     T_l = sum_{i >= l} S_i (6-step suffix scan),  V_l = 8 * [l >= 1] T_l + W_l,  W_seg = sum_l V_l (6-step butterfly)
-// because sum_l l*S_l = sum_{l >= 1} T_l.  Level B: one wave per window does the same over the <= 64 segment pairs with
-// weight 512 and adds S once more (bucket b holds digit magnitude b+1).  Chain: 26 additions + 3 doublings, then
-// 14 additions + 9 doublings.
-// ================================================================================================
-__device__ __forceinline__ ge_p3 p3_shfl_down64(const ge_p3 &a, int d, int lane) {
-    ge_p3 o;
-    for (int i = 0; i < 10; i++) {
-        o.X.v[i] = __shfl_down(a.X.v[i], d, 64); o.Y.v[i] = __shfl_down(a.Y.v[i], d, 64);
-        o.Z.v[i] = __shfl_down(a.Z.v[i], d, 64); o.T.v[i] = __shfl_down(a.T.v[i], d, 64);
-    }
-    const bool in = lane + d < 64;
-    const ge_p3 id = ge_identity();
-    for (int i = 0; i < 10; i++) {
-        o.X.v[i] = in ? o.X.v[i] : id.X.v[i]; o.Y.v[i] = in ? o.Y.v[i] : id.Y.v[i];
-        o.Z.v[i] = in ? o.Z.v[i] : id.Z.v[i]; o.T.v[i] = in ? o.T.v[i] : id.T.v[i];
-    }
-    return o;
-}
-__device__ __forceinline__ ge_p3 p3_shfl_xor64(const ge_p3 &a, int d) {
-    ge_p3 o;
-    for (int i = 0; i < 10; i++) {
-        o.X.v[i] = __shfl_xor(a.X.v[i], d, 64); o.Y.v[i] = __shfl_xor(a.Y.v[i], d, 64);
-        o.Z.v[i] = __shfl_xor(a.Z.v[i], d, 64); o.T.v[i] = __shfl_xor(a.T.v[i], d, 64);
-    }
-    return o;
-}
-// in: lane l holds (S_l, W_l).  out (every lane): S = sum_l S_l is in lane 0's S; W = sum_l W_l + 2^shift * sum_l l*S_l in every lane
-__device__ __forceinline__ void wave_weighted_sum(ge_p3 &S, ge_p3 &W, int shift, int lane) {
-#pragma unroll 1
-    for (int d = 1; d < 64; d <<= 1) S = ge_add(S, p3_shfl_down64(S, d, lane));      // S_l <- sum_{i >= l} S_i
-    ge_p3 V = S;
-    {
-        const ge_p3 id = ge_identity();
-        const bool keep = lane >= 1;
-        for (int i = 0; i < 10; i++) {
-            V.X.v[i] = keep ? V.X.v[i] : id.X.v[i]; V.Y.v[i] = keep ? V.Y.v[i] : id.Y.v[i];
-            V.Z.v[i] = keep ? V.Z.v[i] : id.Z.v[i]; V.T.v[i] = keep ? V.T.v[i] : id.T.v[i];
-        }
-    }
-    V = ge_mul_by_pow_2(V, shift);
-    V = ge_add(V, W);
-#pragma unroll 1
-    for (int d = 32; d > 0; d >>= 1) V = ge_add(V, p3_shfl_xor64(V, d));
-    W = V;
-}
-// level A: block (one wave) = segment `seg` of window k.  direct: the window has a single segment, write col_k itself.
-// bad_ws (may be null): the sort's "a scalar has bit 255 set" word, ORed into the slot's flag 0 (the sort does not touch the slot)
-__global__ void __launch_bounds__(64) k_reduce_a(const u32 *__restrict__ buckets, int half, int nseg, int lb, u32 *__restrict__ SW, u32 *__restrict__ cols, int direct,
-                                                 const u32 *__restrict__ bad_ws) {
-    C25519_PRIO_SIDE();
-    const int k = blockIdx.x / nseg, seg = blockIdx.x % nseg, lane = threadIdx.x;
-    if (bad_ws && blockIdx.x == 0 && lane == 0 && *bad_ws) atomicOr(cols + MSM_MAX_WIN * 40, 1u);
-    const int LB = 1 << lb, b0 = (seg * 64 + lane) * LB;
-    const u32 *B = buckets + (u64)k * half * 40;
-    const ge_p3 id = ge_identity();
-    ge_p3 run = (b0 + LB - 1 < half) ? p40_load(B, b0 + LB - 1) : id;
-    ge_p3 acc = run;
-#pragma unroll 1
-    for (int j = LB - 2; j >= 1; j--) {
-        run = ge_add(run, (b0 + j < half) ? p40_load(B, b0 + j) : id);
-        acc = ge_add(acc, run);
-    }
-    run = ge_add(run, (b0 < half) ? p40_load(B, b0) : id);
-    wave_weighted_sum(run, acc, lb, lane);                // run (lane 0) = S_seg, acc = W_seg = sum (b - seg base) B_b
-    if (lane == 0) {
-        if (direct) p40_store(cols, k, ge_add(acc, run));
-        else { p40_store(SW, 2 * (u64)blockIdx.x, run); p40_store(SW, 2 * (u64)blockIdx.x + 1, acc); }
-    }
-}
-// level B: one wave per window over its nseg <= 64 segment pairs
-__global__ void __launch_bounds__(64) k_reduce_b(const u32 *__restrict__ SW, int nseg, int lb, u32 *__restrict__ cols) {
-    C25519_PRIO_SIDE();
-    const int k = blockIdx.x, lane = threadIdx.x;
-    const ge_p3 id = ge_identity();
-    ge_p3 S = lane < nseg ? p40_load(SW, 2 * ((u64)k * nseg + lane)) : id;
-    ge_p3 W = lane < nseg ? p40_load(SW, 2 * ((u64)k * nseg + lane) + 1) : id;
-    wave_weighted_sum(S, W, lb + 6, lane);                    // 64 x 2^lb buckets per segment
-    if (lane == 0) p40_store(cols, k, ge_add(W, S));
-}
+// (the bucket reduction, col_k = sum_b (b+1) * B_b [pippenger.rs:146-151], lives in reduce.hip: k_reduce_a4 / k_reduce_b4)
 
 // ================================================================================================
 // result slots and partial-result RECORDS
@@ -522,26 +428,6 @@ void msm_layout(uint64_t n, msm_geom &g, int cmax_call, int c_exact) {
     for (int k = g.nwin; k < MSM_MAX_WIN; k++) { g.pos[k] = 0; g.wid[k] = 1; }
     msm_slice_params(g);
     for (int i = 0; i < 8; i++) g.addk[i] = a[i];
-    g.ngroups = 1; g.gstart[0] = 0;
-    for (int i = 1; i <= MSM_MAX_GROUPS; i++) g.gstart[i] = (unsigned char)g.nwin;
-}
-// Window groups of a single-pass call (msm_geom): `groups` groups of consecutive windows; `last` (0 = equal shares) = content windows of the final
-// group, whose bucket reduction is the exposed tail of the call.  The overflow window (a handful of entries) rides with the final group.  Only layouts
-// whose windows have at least 1024 buckets (a block of the bucket-order kernel must not straddle groups) and at least two windows per group.
-void msm_set_groups(msm_geom &g, int groups, int last) {
-    g.ngroups = 1; g.gstart[0] = 0;
-    for (int i = 1; i <= MSM_MAX_GROUPS; i++) g.gstart[i] = (unsigned char)g.nwin;
-    groups = std::min(groups, MSM_MAX_GROUPS);
-    const int content = g.nwin - 1;
-    if (groups < 2 || g.half < 1024 || content < 2 * groups) return;
-    if (last < 1 || last > content - (groups - 1)) last = 0;
-    int at = 0;
-    for (int q = 0; q < groups - 1; q++) {
-        const int left = content - at - last, share = last ? (left + (groups - 2 - q)) / (groups - 1 - q) : (content - at + (groups - 1 - q)) / (groups - q);
-        at += share;
-        g.gstart[q + 1] = (unsigned char)at;
-    }
-    g.ngroups = (unsigned char)groups;
 }
 // diagnostics (host only, no GPU needed): the layout the MSM would use for n terms
 EXPORT int32_t c25519_msm_geometry(uint64_t n, int32_t *c, int32_t *nwin, uint8_t *pos, uint8_t *wid, uint32_t *addk) {
@@ -611,49 +497,32 @@ int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_plan &pl, const uint32_t *d_p
     //  the next pass -- 18.2 - 20.3 ms per 2^24 terms against 16.5; 512-thread blocks, i.e. two waves per SIMD with 176
     //  registers: 16.9 - 17.0 against 16.6 - 16.9; an LDS reservation to the same effect: 16.2 against 15.9; four waves per SIMD
     //  without a prefetched record: 16.0 / 15.5 against 15.1 - 15.3; un-serialised accumulations of neighbouring passes: +3 - 9 %)
-    static const int coop_reduce = C25519_KNOB("REDUCE_COOP", 1);     // A/B knob: 0 = rounds 2-3's one-lane-per-point reduction (k_reduce_a / k_reduce_b below)
-    // Window groups (msm_geom, single-pass calls): k_accumulate is launched once per group on the main stream -- the groups' stretches of the bucket
-    // order are separate -- and the second (high-priority) stream reduces group q as soon as ITS accumulation has finished, beside the accumulation
-    // of group q + 1: what remains exposed at the end of the call is the reduction of the last group only.
-    const int groups = (g.ngroups > 1 && reduce && !cont && coop_reduce) ? g.ngroups : 1;
     // (r5) A call of ONE pass has no other stream set to compete with: its reduction goes on the MAIN stream, straight behind the accumulation, and the
     // read-back behind the reduction -- two cross-stream hand-overs (12 + 20 us of event latency: gpurun_out/r05_timeline_*) less on the critical path
     // of every single-pass call.  The long-bucket kernels stay on the second stream (they run beside the accumulation); the main stream waits for them
     // before the reduction -- long since finished.
     static const int reduce_main = C25519_KNOB("REDUCE_MAIN", 1);       // A/B knob: 0 = always on the second stream (rounds 3-4)
-    const bool red_main = reduce_main && ctx->solo && reduce && !cont && groups == 1 && coop_reduce && !wait_acc;
-    for (int q = 0; q < groups; q++) {
-        const int k0 = groups > 1 ? g.gstart[q] : 0, k1 = groups > 1 ? g.gstart[q + 1] : g.nwin;
-        ctx->kname[0] = launch_accumulate(d_pts, pl.sorted, pl.base, pl.perm + (size_t)k0 * g.half, (uint64_t)(k1 - k0) * g.half, pl.n, g, pl.buckets, cont ? 1 : 0, st);
-        if (groups > 1) {
-            HIPCHK(hipEventRecord(ctx->ev_grp[q], st));
-            HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_grp[q], 0));        // (behind the long-bucket kernels the second stream already holds)
-            launch_bucket_reduce4(pl.buckets, g, pl.nseg, pl.SW, d_slot, d_bad_sticky ? d_bad_sticky : pl.bad_ws, ctx->aux, k0, k1);
-            HIPCHK(hipGetLastError());
-        }
-    }
+    const bool red_main = reduce_main && ctx->solo && reduce && !cont && !wait_acc;
+    // (one launch over all windows: accumulating and reducing a single-pass call in window groups was measured and not adopted, profiles/r05_ab_window_groups.txt)
+    ctx->kname[0] = launch_accumulate(d_pts, pl.sorted, pl.base, pl.perm, (uint64_t)g.nwin * g.half, pl.n, g, pl.buckets, cont ? 1 : 0, st);
     HIPCHK(hipEventRecord(ctx->ev_acc, st));
     if (ring) HIPCHK(hipEventRecord(ring[1], st));
-    // The bucket reduction runs on the SECOND (high-priority) stream, behind the long-bucket kernels it depends on anyway.  On the
-    // main stream its few small blocks had normal priority: once the sort of the next pass stopped being late (round 3) the next
-    // accumulation -- on the other stream set -- began before they were dispatched, refilled every hole a retiring block left, and
-    // k_reduce_b waited 1.1 ms for its 17 wave slots, holding back this stream set's next pass (profiles/r03_msm_2p24_timeline.txt).
+    const uint32_t *bad = d_bad_sticky ? d_bad_sticky : pl.bad_ws;
     if (red_main) {
         HIPCHK(hipEventRecord(ctx->ev_join, ctx->aux));          // behind the long-bucket kernels
         HIPCHK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-        launch_bucket_reduce4(pl.buckets, g, pl.nseg, pl.SW, d_slot, d_bad_sticky ? d_bad_sticky : pl.bad_ws, st);
+        launch_bucket_reduce4(pl.buckets, g, pl.nseg, pl.SW, d_slot, bad, st);
         HIPCHK(hipGetLastError());
         if (ring) HIPCHK(hipEventRecord(ring[2], st));
         return C25519_OK;
     }
-    if (reduce && groups == 1) HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_acc, 0));      // (without a reduction nothing on the second stream needs the accumulated buckets)
-    if (groups > 1) {
-    } else if (reduce && coop_reduce) {
-        launch_bucket_reduce4(pl.buckets, g, pl.nseg, pl.SW, d_slot, d_bad_sticky ? d_bad_sticky : pl.bad_ws, ctx->aux);
-        HIPCHK(hipGetLastError());
-    } else if (reduce) {
-        hipLaunchKernelGGL(k_reduce_a, dim3((unsigned)(g.nwin * pl.nseg)), dim3(64), 0, ctx->aux, pl.buckets, g.half, pl.nseg, red_lb_log2(g.half), pl.SW, d_slot, pl.nseg == 1 ? 1 : 0, d_bad_sticky ? d_bad_sticky : pl.bad_ws);
-        if (pl.nseg > 1) hipLaunchKernelGGL(k_reduce_b, dim3((unsigned)g.nwin), dim3(64), 0, ctx->aux, pl.SW, pl.nseg, red_lb_log2(g.half), d_slot);
+    // Otherwise the bucket reduction runs on the SECOND (high-priority) stream, behind the long-bucket kernels it depends on anyway.  On the
+    // main stream its few small blocks had normal priority: once the sort of the next pass stopped being late (round 3) the next
+    // accumulation -- on the other stream set -- began before they were dispatched, refilled every hole a retiring block left, and
+    // the reduction waited 1.1 ms for its 17 wave slots, holding back this stream set's next pass (profiles/r03_msm_2p24_timeline.txt).
+    if (reduce) {                                                // (without a reduction nothing on the second stream needs the accumulated buckets)
+        HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_acc, 0));
+        launch_bucket_reduce4(pl.buckets, g, pl.nseg, pl.SW, d_slot, bad, ctx->aux);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(ctx->ev_join, ctx->aux));
@@ -962,11 +831,10 @@ int32_t prep_points_on(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n, int
         // points per lane and inversion: 64 when the launch still has >= 2048 waves (the records of the later passes of a
         // multi-pass call; 2^24 terms: 15.8 ms with 16 everywhere, 15.3 with 64), 32 from 2^20 points (profiles/r04_ab_prep_points_per_lane.txt:
         // 2^20 terms 1.10 against 1.18 ms, 2^21 the same either way), 16 below (2^19: 0.76 against 0.81 ms; 8 and 4 buy nothing down to 2^16)
-        static const int ch_knob = C25519_KNOB("PREP_CH", 0);             // A/B knob: 4 / 8 / 16 / 32 / 64
         // below 2^18 points the kernel is a latency chain (the lane's prefix products, ONE inversion, the unwinding): 4 points per lane shorten it
         // (2^13 terms 0.48 -> 0.40 ms, 2^16 0.54 -> 0.51)
-        const int CH = ch_knob ? ch_knob : (n >= (1ull << 23) ? 64 : n >= (1ull << 20) ? 32 : n >= (1ull << 18) ? 16 : 4);
-        constexpr int wpb = 4;
+        const int CH = n >= (1ull << 23) ? 64 : n >= (1ull << 20) ? 32 : n >= (1ull << 18) ? 16 : 4;
+        constexpr int wpb = PREP_WPB;
         const unsigned blocks = (unsigned)div_up64((n + CH - 1) / CH, 64 * wpb);
         // the prefix buffer is addressed per wave (CH x 3 x 64 pieces): blocks x wpb waves of them
         r = ctx_reserve(ctx, pre, (size_t)blocks * wpb * CH * 3 * 64 * 16);
@@ -977,32 +845,20 @@ int32_t prep_points_on(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n, int
             if (n >= (1ull << 18)) {
                 const unsigned bl = (unsigned)div_up64((n + 7) / 8, 64 * wpb);
                 if ((r = ctx_reserve(ctx, pre, (size_t)bl * wpb * 8 * 3 * 64 * 16))) return r;
-                hipLaunchKernelGGL((k_prep_raw2<8, wpb, 0, 1>), dim3(bl), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
+                hipLaunchKernelGGL((k_prep_raw2<8, 1>), dim3(bl), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
             } else {
                 const unsigned bl = (unsigned)div_up64((n + 3) / 4, 64 * wpb);
                 if ((r = ctx_reserve(ctx, pre, (size_t)bl * wpb * 4 * 3 * 64 * 16))) return r;
-                hipLaunchKernelGGL((k_prep_raw2<4, wpb, 0, 1>), dim3(bl), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
+                hipLaunchKernelGGL((k_prep_raw2<4, 1>), dim3(bl), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
             }
             HIPCHK(hipGetLastError());
             return C25519_OK;
         }
-        // A/B proxy (profiles/r04_ab_prep_two_waves.txt): what the normaliser's memory system does with TWO waves per compute unit -- the occupancy
-        // an LDS-resident inversion tree (prefix products of 16 points per lane kept in LDS: 40 KB per wave) would leave it
-        static const int two_waves = C25519_KNOB("PREP_TWO_WAVES", 0);
-        static const int prep_nt = C25519_KNOB("PREP_NT", 0);             // A/B knob: 1 = streaming accesses for the normaliser's inputs and prefix scratch (large launches)
-        if (two_waves && CH == 16) {
-            const unsigned b2 = (unsigned)div_up64((n + CH - 1) / CH, 64 * 2);
-            if ((r = ctx_reserve(ctx, pre, (size_t)b2 * 2 * CH * 3 * 64 * 16))) return r;
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_prep_raw2<16, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-            hipLaunchKernelGGL((k_prep_raw2<16, 2>), dim3(b2), dim3(128), 100 * 1024, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
-        } else
-        if (CH == 64 && prep_nt) hipLaunchKernelGGL((k_prep_raw2<64, wpb, 1>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
-        else if (CH == 32 && prep_nt) hipLaunchKernelGGL((k_prep_raw2<32, wpb, 1>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
-        else if (CH == 64) hipLaunchKernelGGL((k_prep_raw2<64, wpb>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
-        else if (CH == 32) hipLaunchKernelGGL((k_prep_raw2<32, wpb>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
-        else if (CH == 8) hipLaunchKernelGGL((k_prep_raw2<8, wpb>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
-        else if (CH == 4) hipLaunchKernelGGL((k_prep_raw2<4, wpb>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
-        else hipLaunchKernelGGL((k_prep_raw2<16, wpb>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
+        // (measured and not adopted: two waves per compute unit, profiles/r04_ab_msm_structure.txt; streaming accesses, profiles/r06_ab_mall.txt)
+        if (CH == 64) hipLaunchKernelGGL((k_prep_raw2<64>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
+        else if (CH == 32) hipLaunchKernelGGL((k_prep_raw2<32>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
+        else if (CH == 4) hipLaunchKernelGGL((k_prep_raw2<4>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
+        else hipLaunchKernelGGL((k_prep_raw2<16>), dim3(blocks), dim3(64 * wpb), 0, st, d_points, n, (uint32_t *)pre.p, d_pts, dst0);
     } else return bad_arg(ctx, "msm: bad in_fmt");
     HIPCHK(hipGetLastError());
     return C25519_OK;
@@ -1067,7 +923,7 @@ hipEvent_t *pass_ring(c25519_ctx *owner, c25519_ctx *c, uint8_t kind) {
 struct pts_ahead { uint32_t *pts; uint64_t n, offset; hipEvent_t done; bool launch; };
 static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const msm_geom &g, uint64_t terms, uint32_t *d_slot,
                                 hipEvent_t wait_acc, const pts_ahead *ahead = nullptr, hipEvent_t wait_in = nullptr,
-                                bool cont = false, bool reduce = true, uint64_t n_carve = 0, uint32_t *d_bad_sticky = nullptr, int parity = -1) {
+                                bool cont = false, bool reduce = true, uint64_t n_carve = 0, uint32_t *d_bad_sticky = nullptr) {
     int32_t r;
     uint32_t *d_pts;
     if (wait_in) HIPCHK(hipStreamWaitEvent(ctx->stream, wait_in, 0));      // host-pointer calls: this pass's inputs are still on their way up
@@ -1080,21 +936,14 @@ static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_
     HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));     // the sort does not touch the slot: it need not wait for k_slot_init's dispatch
     // A continuing pass on device-resident inputs does not wait for its predecessor on this stream set with the first half of its SORT
     // (k_sweep_local, k_bin_totals: scalars in, sort scratch out -- consumed by kernels that precede it on the second stream); only the
-    // second half (k_part2g on) overwrites the lists the predecessor's accumulation reads and waits for it -- or not even that, when the lists
-    // exist twice (parity).  Before, the whole sort waited: its 1024-thread blocks found no room beside the OTHER set's accumulation, ended in
-    // that kernel's tail, and every second accumulation started ~0.4 ms late (profiles/r04_msm_2p24_last_call_timeline.txt: gaps of
-    // 35 / 420 us alternating; with the partition ahead 30 - 190 us, profiles/r04_msm_2p24_sort_ahead_timeline.txt).
-    // C25519_SWEEP_EARLY: 0 = round 3's order, 1 (default) = only the partition half (k_sweep_local, k_bin_totals: sort scratch only) runs ahead,
-    // 2 = all of it.  profiles/r04_ab_sort_ahead.txt: 13.39 - 13.51 ms against 13.69 - 13.71 on one box, 13.93 - 14.00 against 13.93 - 14.11 on
-    // another; 1 and 2 measure the same (the accumulation beside a sort stretches by what the sort no longer costs afterwards), so the
-    // default is the one without a second copy of the lists.
-    static const int sweep_early = C25519_KNOB("SWEEP_EARLY", 1);
-    const bool early = sweep_early && cont && !wait_in && terms > msm_small_max() && parity >= 0;
-    hipEvent_t lists_free = nullptr;
-    if (parity >= 0) {
-        HIPCHK(hipEventRecord(ctx->ev_lists[parity & 1], ctx->stream));                 // the accumulation before this pass (list copy parity ^ 1) is behind this point
-        if (early) lists_free = sweep_early >= 2 ? ctx->ev_lists[(parity & 1) ^ 1] : ctx->ev_fork;   // (copy `parity` was last read two passes ago: implied by the stream order, stated anyway)
-    }
+    // second half (k_part2g on) overwrites the lists the predecessor's accumulation reads and waits for it (lists_free).  Before, the whole sort
+    // waited: its 1024-thread blocks found no room beside the OTHER set's accumulation, ended in that kernel's tail, and every second accumulation
+    // started ~0.4 ms late (profiles/r04_msm_2p24_last_call_timeline.txt: gaps of 35 / 420 us alternating; with the partition ahead 30 - 190 us,
+    // profiles/r04_msm_2p24_sort_ahead_timeline.txt).  profiles/r04_ab_sort_ahead.txt: 13.39 - 13.51 ms against 13.69 - 13.71 on one box, 13.93 - 14.00
+    // against 13.93 - 14.11 on another; the whole sort ahead on a second copy of the lists measured the same and is not kept.
+    // (a continuing pass exists only in a call with more passes than stream sets: msm_record_enqueue)
+    const bool early = cont && !wait_in && terms > msm_small_max();
+    const hipEvent_t lists_free = early ? ctx->ev_fork : nullptr;
     if (!early) HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
     if (!cont && !ctx->direct_seq) slot_init(d_slot, terms, nullptr, ctx->stream, g.c);            // (a continuing pass adds its counters to the slot of its stream set; a directly published small pass writes its whole record itself)
     if (terms <= msm_small_max() && g.half <= 64 && g.nwin <= 64 && !cont && reduce && !ahead) {      // (g: a forced width may not be the small path's -- then the bucket pipeline serves)
@@ -1108,25 +957,14 @@ static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_
     pl.bad_sticky = d_bad_sticky;
     // (normalisation first, then the sort on the second stream: 2.26 against 2.34 ms at 2^21 terms the other way round)
     static const int serial_sort = C25519_KNOB("PROFILE_SERIAL_SORT", 0);     // profiling: the sort only starts after the normaliser, so that its kernels can be timed alone
-    // SORT_FIRST (A/B knob): 1 = the sort is enqueued (second, high-priority stream) BEFORE the normaliser, so that its first kernel -- whose
-    // 1024-thread blocks of 128 VGPRs need an empty compute unit -- is dispatched first instead of picking up the compute units the normaliser's
-    // blocks leave one by one; 2 = the normaliser additionally waits for the partition half of the sort (k_sweep_local, k_bin_totals).
-    // Measured and NOT adopted (profiles/r05_ab_window_groups.txt): one box 2.00 -> 1.92 ms per 2^21 terms, another 1.85 -> 1.89, four interleaved
-    // repetitions on a third 1.959 (normaliser first) against 1.993; 2^20 level, 2^18 +2 %.  The default stays 0.
-    static const int sort_first = C25519_KNOB("SORT_FIRST", 0);
-    const bool sorted_first = sort_first && !ahead && !serial_sort && !cont && !wait_in;      // (measured on device-resident single / first passes only)
-    if (sorted_first) {
-        pl.ev_partition = nullptr;
-        if ((r = msm_enqueue_sort(ctx, d_scalars, n, g, d_slot, ctx->aux, pl, nullptr, n_carve, lists_free, sweep_early >= 2 ? parity : -1))) return r;
-        if (pl.ev_partition) HIPCHK(hipStreamWaitEvent(ctx->stream, pl.ev_partition, 0));
-    }
+    // (the sort enqueued ahead of the normaliser: measured and not adopted, profiles/r05_ab_window_groups.txt)
     if (!ahead) { if ((r = prep_points(ctx, d_points, n, in_fmt, d_pts, 0, slot_flags(d_slot) + 1))) return r; }
     else if (ahead->launch) {
         if ((r = prep_points(ctx, d_points, ahead->n, in_fmt, ahead->pts, 0, slot_flags(d_slot) + 1))) return r;
         HIPCHK(hipEventRecord(ahead->done, ctx->stream));
     } else HIPCHK(hipStreamWaitEvent(ctx->stream, ahead->done, 0));
     if (serial_sort) { HIPCHK(hipEventRecord(ctx->ev_z, ctx->stream)); HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_z, 0)); }
-    if (!sorted_first && (r = msm_enqueue_sort(ctx, d_scalars, n, g, d_slot, ctx->aux, pl, nullptr, n_carve, lists_free, sweep_early >= 2 ? parity : -1))) return r;
+    if ((r = msm_enqueue_sort(ctx, d_scalars, n, g, d_slot, ctx->aux, pl, nullptr, n_carve, lists_free))) return r;
     // a continuing pass adds onto the bucket sums its predecessor on this stream set left: they must be where it left them
     if (cont && pl.buckets != ctx->cont_buckets) return bad_arg(ctx, "msm: internal error (the workspace of a continuing pass moved its buckets)");
     ctx->cont_buckets = pl.buckets;
@@ -1229,15 +1067,6 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
     // carries the number the layout was derived from (records_fold re-derives it from there).
     const uint64_t layout_terms = (passes > (uint64_t)ps.lanes && per >= (1ull << 20)) ? std::max<uint64_t>(per, 1ull << 21) : per;
     msm_layout(layout_terms, g);
-    // A/B knobs (tuning build): window groups of a single-pass call (msm_geom / msm_enqueue_acc), ACC_LAST = content windows of the final group
-    // Measured and NOT adopted (profiles/r05_ab_window_groups.txt): with two groups the exposed tail of a 2^21-term call shrinks from 0.26 to 0.18 ms, but
-    // the reduction of group 0 takes its issue slots and registers from the second group's accumulation (k_accumulate 1.16 -> 1.17 - 1.26 ms over the two
-    // launches, each with its own ramp-down): four interleaved repetitions on one box give 1.959 ms (one group) against 1.965 (two); three and four
-    // groups 2.06 / 2.18; at 2^20 and 2^18 terms two groups lose 8 % and 17 %.  The default stays ONE group.
-    static const int acc_groups = std::min(2, C25519_KNOB("ACC_GROUPS", 1)), acc_last = 0;      // (three / four groups and an uneven last group lost twice and left the build: profiles/r05_ab_window_groups.txt)
-    // (groups exist in the chunk-local sort only: single passes below its lower boundary -- the digit-matrix sort's range -- keep one group)
-    static const uint64_t chunk_local_min = (uint64_t)C25519_KNOB("SORT_CHUNK_LOCAL_MIN", 1 << 16);
-    if (passes == 1 && n > msm_small_max() && n >= chunk_local_min) msm_set_groups(g, acc_groups, acc_last);
     ctx->solo = passes == 1;               // (overwritten by every call: an early error return leaves nothing behind that a later call would read)
     hipEvent_t prev_acc = nullptr;                         // the accumulation of the previous pass (on the other stream set)
     hipEvent_t prev_acc_last = nullptr;
@@ -1262,7 +1091,7 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
         hipEvent_t in_ev = nullptr;
         if (fetch && (r = (*fetch)(lo, m, &in_ev))) return r;
         if ((r = msm_pass_enqueue(ctx, c, d_scalars + lo * 32, d_points + lo * psz, m, in_fmt, g, layout_terms, slot, prev_acc, (ahead && p >= 1) ? &ah : nullptr, in_ev,
-                                  !first, last, per, sticky, passes > (uint64_t)L ? (int)((p / L) & 1) : -1))) {
+                                  !first, last, per, sticky))) {
             if (ctx->err.empty()) ctx->err = c->err;
             return r;
         }

@@ -51,18 +51,13 @@ namespace c25519 {
 //  anyway (bad_scalar); a term beyond n is loaded as s = 0, whose digits are all zero: s' = addk puts 2^(wid-1) into every signed
 //  window and 0 into the unsigned ones -- it is skipped like any zero digit)
 struct sweep_regs { u32 s[SWEEP_TPT][8]; };
-typedef unsigned int sweep_u32x4 __attribute__((ext_vector_type(4)));
 template <int THREADS>
-__device__ __forceinline__ void sweep_load(const uint8_t *__restrict__ scalars, u64 n, u64 lo, const msm_geom &g, sweep_regs &R, u32 *__restrict__ bad_scalar, int nt) {
+__device__ __forceinline__ void sweep_load(const uint8_t *__restrict__ scalars, u64 n, u64 lo, const msm_geom &g, sweep_regs &R, u32 *__restrict__ bad_scalar) {
 #pragma unroll
     for (int r = 0; r < SWEEP_TPT; r++) {
         const u64 t = lo + (u64)r * THREADS + threadIdx.x;
         u32 w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (t < n && nt) {                                     // (r6, A/B knob SWEEP_NT: the scalars are read once per pass -- streaming policy, see msm.hip k_prep_raw2)
-            const sweep_u32x4 *q = reinterpret_cast<const sweep_u32x4 *>(scalars) + 2 * t;
-            const sweep_u32x4 a = __builtin_nontemporal_load(q), b = __builtin_nontemporal_load(q + 1);
-            w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-        } else if (t < n) load8(scalars, t, w);
+        if (t < n) load8(scalars, t, w);
         if (bad_scalar && (w[7] >> 31)) atomicOr(bad_scalar, 1u);
         u32 carry = 0;
 #pragma unroll
@@ -91,11 +86,11 @@ __device__ __forceinline__ u32 sweep_take(sweep_regs &R, int r, int wd) {
 // zeroed here by block 0 instead of a memset of their own: beside k_accumulate every extra launch of the chain waits 30 - 180 us for
 // a dispatch slot.  bad_blk[j] = 1 if a scalar of chunk j has bit 255 set (k_bin_totals ORs them into one word, the bucket
 // reduction ORs that into the result slot: the sort itself never touches the slot).
-// THREADS: 1024 (a chunk of 8192 terms per block: the shape that is fastest ALONE) or 256 (2048 terms: one wave per SIMD and 13 KB of LDS,
-// the shape that FITS beside a k_accumulate held at two waves per SIMD -- profiles/r04_ab_sort_beside_accumulate.txt)
+// THREADS: 1024 (a chunk of 8192 terms per block: the shape that is fastest alone; smaller blocks that fit beside a k_accumulate held at two
+// waves per SIMD were measured and not adopted -- profiles/r04_ab_sort_beside_accumulate.txt)
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) k_sweep_local(const uint8_t *__restrict__ scalars, u64 n, msm_geom g, int SL, u32 *__restrict__ lsg, u32 *__restrict__ bad_blk,
-                                                               u32 *__restrict__ P1, u64 wstride, u32 *__restrict__ zero_words, int nzero, int nt) {
+                                                               u32 *__restrict__ P1, u64 wstride, u32 *__restrict__ zero_words, int nzero) {
     C25519_PRIO_CHAIN();
     extern __shared__ u32 sm[];
     constexpr int NW = THREADS / 64, CHUNK = THREADS * SWEEP_TPT;
@@ -114,7 +109,7 @@ __global__ void __launch_bounds__(THREADS) k_sweep_local(const uint8_t *__restri
     __syncthreads();
     const u64 lo = (u64)j * CHUNK;
     sweep_regs R;
-    sweep_load<THREADS>(scalars, n, lo, g, R, &sbad, nt);
+    sweep_load<THREADS>(scalars, n, lo, g, R, &sbad);
 #pragma unroll 1
     for (int k = 0; k < g.nwin; k++) {
         const int wd = g.wid[k], bps = g.bps[k];
@@ -163,7 +158,7 @@ __global__ void __launch_bounds__(THREADS) k_sweep_local(const uint8_t *__restri
         const u32 tot = ls[SL];
         u32 *dst = P1 + (u64)k * wstride + (u64)j * CHUNK;
         for (u32 i = threadIdx.x; i < tot; i += THREADS) dst[i] = stage[i];
-        for (int i = threadIdx.x; i <= SL; i += THREADS) lsg[((u64)k * (SL + 1) + i) * nchunk + j] = ls[i];      // (SL can be 256 = THREADS of the small shape)
+        for (int i = threadIdx.x; i <= SL; i += THREADS) lsg[((u64)k * (SL + 1) + i) * nchunk + j] = ls[i];
     }
     if (threadIdx.x == 0) bad_blk[j] = sbad;
 }
@@ -195,8 +190,7 @@ __global__ void __launch_bounds__(256) k_bin_totals(const u32 *__restrict__ lsg,
 // to count, and (from L2 now) to place: 32 pieces in registers with static indices need more than the 64 VGPRs two 1024-thread
 // blocks per compute unit leave a lane (42 spilled).  A bin with more than P2G_ITER pieces per wave or more than PART_CAP entries --
 // heavily skewed digits -- walks its chunks without the list and places its entries straight into the sorted array.
-// NW waves per block (16: two blocks per CU; 8: 512 threads, two waves per SIMD at 56 VGPRs -- fits beside k_accumulate at two waves per SIMD), ITER:
-// pieces a wave lists; chunk: terms per chunk of the partition that produced P1 (SWEEP_TPT x its block size)
+// NW waves per block (16: two blocks per CU), ITER: pieces a wave lists; chunk: terms per chunk of the partition that produced P1 (SWEEP_TPT x its block size)
 template <int NW, int ITER>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 2, NW / 2)))
 k_part2g(const u32 *__restrict__ P1, u64 n, u64 wstride, u32 chunk, msm_geom g, int SL, int nchunk, const u32 *__restrict__ lsg, const u32 *__restrict__ binm,
@@ -245,7 +239,7 @@ k_part2g(const u32 *__restrict__ P1, u64 n, u64 wstride, u32 chunk, msm_geom g, 
         // block's share of them (the bucket order and the accumulation walk ALL half buckets of every window)
         const int per = (1 << g.bps_log2) - PART_BPS, first = (SL << g.bps[k]) + sidx * per;
         for (int i = tid; i < per; i += 64 * NW) { totals[(u64)k * g.half + first + i] = 0; base[(u64)k * (g.half + 1) + first + i] = wtot; }
-        if (per > 0 && tid == 0) atomicAdd(&ord_hist[256 * msm_group_of(g, k) + 255], (u32)per);      // (length class of an empty list; one histogram per window group)
+        if (per > 0 && tid == 0) atomicAdd(&ord_hist[255], (u32)per);      // (length class of an empty list)
     }
     u32 *dst = sorted + (u64)k * n + b0;
     if (fits) {
@@ -287,7 +281,7 @@ k_part2g(const u32 *__restrict__ P1, u64 n, u64 wstride, u32 chunk, msm_geom g, 
     __syncthreads();
     if (tid < PART_BPS) order_note_bucket(cnt[tid], (u64)k * g.half + (u64)sidx * PART_BPS + tid, g, base, oh, max_items, items, counters, long_gids, long_first);
     __syncthreads();
-    if (tid < 256 && oh[tid]) atomicAdd(&ord_hist[256 * msm_group_of(g, k) + tid], oh[tid]);
+    if (tid < 256 && oh[tid]) atomicAdd(&ord_hist[tid], oh[tid]);
     if (fits) {
 #pragma unroll 1
         for (int t0 = 0; t0 < nslots; t0 += 8) {
@@ -333,16 +327,11 @@ k_part2g(const u32 *__restrict__ P1, u64 n, u64 wstride, u32 chunk, msm_geom g, 
 
 // the same with the scan inside: every block scans the 256-bin histogram itself (read-only) and takes its slots from a
 // separate cursor array (zeroed by k_sweep_local) -- one launch less in the chain
-// Window groups (msm_geom): every group has its own length histogram, its own cursors and its own stretch of perm -- the buckets of windows
-// [gstart[q], gstart[q + 1]) in decreasing list length at perm[gstart[q] * half ..) -- so that k_accumulate can be launched group by group.  A block's
-// buckets belong to ONE window (groups are only formed when half >= BS).
 template <int BS>                                            // 256 bins, BS >= 256 threads: a block's buckets per bin take their slots with ONE global atomic per bin
 __global__ void __launch_bounds__(BS) k_order_place(const u32 *__restrict__ totals, u64 nb, const u32 *__restrict__ ord_hist, u32 *__restrict__ ord_cursor, u32 *__restrict__ perm, msm_geom g) {
     C25519_PRIO_CHAIN();
     __shared__ u32 h[256], start[256], basep[256];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int grp = g.ngroups > 1 ? msm_group_of(g, (int)(((u64)blockIdx.x * BS) / (u64)g.half)) : 0;
-    ord_hist += 256 * grp; ord_cursor += 256 * grp; perm += (u64)g.gstart[grp] * (u64)g.half;
     if (threadIdx.x < 256) {
         const u32 mine = ord_hist[threadIdx.x];
         u32 inc = mine;
@@ -409,7 +398,7 @@ void msm_sort_params(uint64_t n, msm_geom &g) {
 // n_carve (0 = n): the number of terms the workspace is carved for -- passes that CONTINUE each other's bucket sums (msm_record_enqueue)
 // must find the buckets at the same address although the last pass is shorter
 int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_scalars, const msm_geom &g, uint32_t *d_slot, hipStream_t sort_stream, msm_plan &pl,
-                         const msm_merged *md, uint64_t n_carve, hipEvent_t lists_free, int parity) {
+                         const msm_merged *md, uint64_t n_carve, hipEvent_t lists_free) {
     (void)d_slot;
     const uint64_t n = md ? (uint64_t)md->K * md->ns : n_scalars;
     const uint64_t nc = n_carve > n ? n_carve : n;
@@ -431,13 +420,9 @@ int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_s
     // workspace carve-up (tmp_d): [digit matrix | counts] (merged layout only) | base | sorted | buckets | segment pairs | flags | perm | long-bucket lists | sort scratch
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    // parity >= 0 (the passes of a multi-pass call): what the accumulation READS of the sort -- bucket bases, gather lists, bucket order -- exists
-    // twice, and the pass uses copy `parity`: the sort of the next pass on this workspace can then run beside this pass's accumulation
-    const int copies = parity >= 0 ? 2 : 1, cp = parity >= 0 ? (parity & 1) : 0;
-    const size_t szB = ((size_t)g.nwin * (g.half + 1) * 4 + 255) & ~(size_t)255, szS = ((size_t)g.nwin * nc * 4 + 255) & ~(size_t)255, szPerm = (nb * 4 + 255) & ~(size_t)255;
-    const size_t oD = carve(matrix ? (size_t)g.nwin * nc * 2 : 0), oC = carve(matrix ? (size_t)g.nwin * nchunk * g.half * 4 : 0), oB = carve(szB * copies) + szB * cp;
-    const size_t oS = carve(szS * copies) + szS * cp, oK = carve(nb * 160), oT = carve(nb * 4);
-    const size_t oSW = carve((size_t)g.nwin * nseg * 2 * 160), oF = carve(16384), oPerm = carve(szPerm * copies) + szPerm * cp;
+    const size_t oD = carve(matrix ? (size_t)g.nwin * nc * 2 : 0), oC = carve(matrix ? (size_t)g.nwin * nchunk * g.half * 4 : 0), oB = carve((size_t)g.nwin * (g.half + 1) * 4);
+    const size_t oS = carve((size_t)g.nwin * nc * 4), oK = carve(nb * 160), oT = carve(nb * 4);
+    const size_t oSW = carve((size_t)g.nwin * nseg * 2 * 160), oF = carve(16384), oPerm = carve(nb * 4);
     // long-bucket path: at most (#entries / LONG_SEG + #long buckets) work items; a long bucket has > LONG_CAP entries
     const uint64_t entries = (uint64_t)g.nwin * nc;
     const uint32_t max_long = (uint32_t)std::min<uint64_t>(nb, entries / g.long_cap + 1);
@@ -445,17 +430,11 @@ int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_s
     const size_t oLI = carve((size_t)max_items * sizeof(long_item)), oLG = carve((size_t)max_long * 4), oLF = carve((size_t)max_long * 4);
     const size_t oLS = carve((size_t)max_items * 160);
     const bool use_part = matrix && g.c >= 13 && n <= (1ull << 23) && n >= (1ull << 16);          // the two-pass partition of the digit-matrix sort
-    // block shapes of the chunk-local sort: the large ones are the fastest alone; the small ones fit beside a k_accumulate held at two waves
-    // per SIMD (one wave per SIMD at 128 VGPRs / two at 56; profiles/r04_ab_sort_beside_accumulate.txt).  Read once per process.
-    static const int small_blocks = C25519_KNOB("SORT_SMALL", 0);
-    // C25519_SWEEP_THREADS=512: the partition in 512-thread blocks (chunks of 4096 terms: two waves per SIMD at 64 VGPRs and 25 KB of LDS) with the
-    // per-bin sort in its large shape (four waves per SIMD at 32 VGPRs, 76 KB) -- the pairing that fits beside a two-wave k_accumulate without
-    // the 16-entry runs of the all-small arm
-    static const int sweep_threads = small_blocks ? 256 : (C25519_KNOB("SWEEP_THREADS", SWEEP_THREADS) == 512 ? 512 : SWEEP_THREADS);
-    const int sweep_chunk = sweep_threads * SWEEP_TPT;
-    const int SL = std::max(1, g.half >> g.bps_log2), PART_CHUNK = matrix ? part_chunk(SL) : sweep_chunk, pchunks = (int)((n + PART_CHUNK - 1) / PART_CHUNK), pchunks_c = (int)((nc + PART_CHUNK - 1) / PART_CHUNK);
+    // (block shapes of the chunk-local sort: 1024-thread blocks, the fastest alone.  256- and 512-thread partition blocks that fit beside a k_accumulate held at
+    //  two waves per SIMD were measured and not adopted: profiles/r04_ab_sort_beside_accumulate.txt)
+    const int SL = std::max(1, g.half >> g.bps_log2), PART_CHUNK = matrix ? part_chunk(SL) : SWEEP_CHUNK, pchunks = (int)((n + PART_CHUNK - 1) / PART_CHUNK), pchunks_c = (int)((nc + PART_CHUNK - 1) / PART_CHUNK);
     // chunk-local form: P1 holds whole chunk blocks, oCC the slice starts [window][SL + 1][chunk], oBB the bin totals and the chunks' flags
-    const size_t p1_words = matrix ? (size_t)g.nwin * nc : (size_t)g.nwin * pchunks_c * sweep_chunk;
+    const size_t p1_words = matrix ? (size_t)g.nwin * nc : (size_t)g.nwin * pchunks_c * SWEEP_CHUNK;
     size_t oP1 = 0, oCC = 0, oBB = 0;
     if (!matrix || use_part) { oP1 = carve(p1_words * 4); oCC = carve((size_t)g.nwin * (SL + 1) * pchunks_c * 4); oBB = carve((size_t)g.nwin * (SL + 1) * 4 + (size_t)pchunks_c * 4); }
     int32_t r = ctx_reserve(ctx, ctx->tmp_d, off);
@@ -465,11 +444,8 @@ int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_s
     // small words of the chain (u32 index): [8..] long-bucket counters, [64..319] bucket-order histogram, [320..575] its cursors,
     // [576] "a scalar has bit 255 set" (ORed into the result slot by the bucket reduction: the sort itself never touches the slot)
     uint32_t *flags = (uint32_t *)(ws + oF), *totals = (uint32_t *)(ws + oT), *ord_hist = flags + 64, *perm = (uint32_t *)(ws + oPerm);
-    // (one 256-bin length histogram and one set of cursors per window group: 64 + 512 G words, G <= MSM_MAX_GROUPS, zeroed by the partition kernel)
-    const int ngr = g.ngroups > 1 ? g.ngroups : 1;
-    uint32_t *ord_cursor = flags + 64 + 256 * ngr, *bad_ws = flags + 64 + 512 * ngr;
-    const int ZERO_WORDS = 64 + 512 * ngr;
-    if (ngr > 1 && (matrix || g.half < 1024)) return bad_arg(ctx, "msm: internal error (window groups outside the chunk-local sort)");
+    uint32_t *ord_cursor = flags + 320, *bad_ws = flags + 576;
+    constexpr int ZERO_WORDS = 576;                          // zeroed by the partition kernel
     pl.g = g; pl.n = n; pl.nb = nb; pl.nseg = nseg; pl.max_items = max_items; pl.max_long = max_long;
     pl.base = base; pl.sorted = sorted; pl.buckets = buckets; pl.perm = perm; pl.SW = (uint32_t *)(ws + oSW); pl.counters = flags + 8; pl.bad_ws = bad_ws;
     pl.items = (long_item *)(ws + oLI); pl.lgids = (uint32_t *)(ws + oLG); pl.lfirst = (uint32_t *)(ws + oLF); pl.segs = (uint32_t *)(ws + oLS);
@@ -484,32 +460,18 @@ int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_s
         return msm_matrix_sort_enqueue(ctx, g, md, pl, a, st);
     }
     uint32_t *P1 = (uint32_t *)(ws + oP1), *lsg = (uint32_t *)(ws + oCC), *binm = (uint32_t *)(ws + oBB), *bad_blk = binm + (size_t)g.nwin * (SL + 1);
-    const uint64_t wstride = (uint64_t)pchunks_c * sweep_chunk;
-    constexpr int ITER_SMALL = 160;                                          // pieces per wave: up to 1024 chunks of 2048 terms over 8 waves
-    const int nw1 = sweep_chunk / SWEEP_TPT / 64;
-    const size_t lds1 = ((size_t)2 * nw1 * SL + SL + 1 + sweep_chunk) * 4;
-    const size_t lds2 = ((size_t)3 * PART_BPS_MAX + PART_CAP + (small_blocks ? 8 * ITER_SMALL : 16 * P2G_ITER)) * 4;
-    static const int sweep_nt = C25519_KNOB("SWEEP_NT", 0);
-    if (small_blocks) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep_local<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_part2g<8, ITER_SMALL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        hipLaunchKernelGGL(k_sweep_local<256>, dim3(pchunks), dim3(256), lds1, st, d_scalars, n, g, SL, lsg, bad_blk, P1, wstride, flags, ZERO_WORDS, sweep_nt);
-    } else if (sweep_threads == 512) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_part2g<16, P2G_ITER>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        hipLaunchKernelGGL(k_sweep_local<512>, dim3(pchunks), dim3(512), lds1, st, d_scalars, n, g, SL, lsg, bad_blk, P1, wstride, flags, ZERO_WORDS, sweep_nt);
-    } else {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep_local<SWEEP_THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_part2g<16, P2G_ITER>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        hipLaunchKernelGGL(k_sweep_local<SWEEP_THREADS>, dim3(pchunks), dim3(SWEEP_THREADS), lds1, st, d_scalars, n, g, SL, lsg, bad_blk, P1, wstride, flags, ZERO_WORDS, sweep_nt);
-    }
+    const uint64_t wstride = (uint64_t)pchunks_c * SWEEP_CHUNK;
+    const size_t lds1 = ((size_t)2 * SWEEP_WAVES * SL + SL + 1 + SWEEP_CHUNK) * 4;
+    const size_t lds2 = ((size_t)3 * PART_BPS_MAX + PART_CAP + 16 * P2G_ITER) * 4;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sweep_local<SWEEP_THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_part2g<16, P2G_ITER>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    hipLaunchKernelGGL(k_sweep_local<SWEEP_THREADS>, dim3(pchunks), dim3(SWEEP_THREADS), lds1, st, d_scalars, n, g, SL, lsg, bad_blk, P1, wstride, flags, ZERO_WORDS);
     hipLaunchKernelGGL(k_bin_totals, dim3((g.nwin * SL + 3) / 4), dim3(256), 0, st, lsg, pchunks, SL, g.nwin * SL, binm, bad_blk, bad_ws, pl.bad_sticky);
-    if (pl.ev_partition) HIPCHK(hipEventRecord(pl.ev_partition, st));
     // lists_free: the partition above writes only the sort's own scratch (chunk blocks, slice starts, bin totals, the small counters of the chain);
     // the gather lists, bucket bases, totals and the bucket order -- what the accumulation of the PREVIOUS pass on this workspace still reads --
     // are written from here on
     if (lists_free) HIPCHK(hipStreamWaitEvent(st, lists_free, 0));
-    if (small_blocks) hipLaunchKernelGGL((k_part2g<8, ITER_SMALL>), dim3(g.nwin, SL), dim3(512), lds2, st, P1, n, wstride, (u32)sweep_chunk, g, SL, pchunks, lsg, binm, totals, base, sorted, ord_hist, max_items, pl.items, pl.counters, pl.lgids, pl.lfirst);
-    else hipLaunchKernelGGL((k_part2g<16, P2G_ITER>), dim3(g.nwin, SL), dim3(1024), lds2, st, P1, n, wstride, (u32)sweep_chunk, g, SL, pchunks, lsg, binm, totals, base, sorted, ord_hist, max_items, pl.items, pl.counters, pl.lgids, pl.lfirst);
+    hipLaunchKernelGGL((k_part2g<16, P2G_ITER>), dim3(g.nwin, SL), dim3(1024), lds2, st, P1, n, wstride, (u32)SWEEP_CHUNK, g, SL, pchunks, lsg, binm, totals, base, sorted, ord_hist, max_items, pl.items, pl.counters, pl.lgids, pl.lfirst);
     hipLaunchKernelGGL(k_order_place<1024>, dim3(div_up64(nb, 1024)), dim3(1024), 0, st, totals, nb, ord_hist, ord_cursor, perm, g);
     HIPCHK(hipGetLastError());
     return C25519_OK;

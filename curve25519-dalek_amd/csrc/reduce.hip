@@ -3,7 +3,7 @@
 // The reduction is a latency chain, not a throughput problem: 1.1 M complete additions per 2^21-term pass are 35 us of multiplier time
 // on this GPU, but as a running sum they are ~50 dependent point operations, and a lone wave issues a v_mad_u64_u32 every 6.4 cycles when it is
 // independent of its predecessors and every 14 when it is not (profiles/r04_instruction_rates.txt) -- 9 M x 100 products per addition make
-// ~4.4 us per link of the chain, 0.25 ms for rounds 2-3's k_reduce_a / k_reduce_b (one lane per point, msm.hip).  Nothing hides beside it: it
+// ~4.4 us per link of the chain, 0.25 ms for rounds 2-3's one-lane-per-point reduction.  Nothing hides beside it: it
 // is the tail of every call (and of every verify_batch).
 //
 // The reference's own answer to "one addition is too slow" is its parallel formulas (docs/parallel-formulas.md:106-213, the AVX2 backend:
@@ -135,7 +135,7 @@ __device__ __forceinline__ void rc_dbl(int role, int lane, u32 *arr, u32 *scratc
 
 __device__ __forceinline__ feT rc_tot(const u32 *tot, int c) { feT r; for (int i = 0; i < 10; i++) r.v[i] = tot[c * 10 + i]; return r; }
 // in: S[l], W[l] for the 64 logical lanes.  out: S[0] = sum_l W_l + 2^shift * sum_l l * S_l (in every lane unless scaled_tot); tot = sum_l S_l (one point, 40 words).
-// (wave_weighted_sum of msm.hip: suffix scan, then sum_l l S_l = sum_{l >= 1} T_l, then a butterfly)
+// (suffix scan, then sum_l l S_l = sum_{l >= 1} T_l, then a butterfly)
 // scaled_tot (r6, late; level A of a two-level reduction): lane 63 of W ends with 2^6 * tot.  Level B weights segment j by j * 2^(lb + 6); with the segment totals
 // arriving pre-multiplied by 2^6 it doubles lb times instead of lb + 6 -- six point operations (~13 us) off the tail of EVERY call of 12 288 terms and more -- and the
 // six doublings cost nothing here: in the butterfly only lane 0's result is used, whose cone of operands at the step of distance d is lanes 0 .. d - 1, so lane 63's
@@ -181,14 +181,13 @@ __device__ __forceinline__ void rc_weighted_sum(int role, int lane, u32 *S, u32 
     }
 }
 // level A: block = segment `seg` (64 x 2^lb buckets, 2^lb per logical lane: 512 / 8, or 1024 / 16 for 17-bit windows) of window k.  direct: the window has a single segment, write col_k itself.
-// k0: first window of the launch (a window group, msm_geom: the blocks of the launch are the segments of windows k0 ..)
 __global__ void __launch_bounds__(256) k_reduce_a4(const u32 *__restrict__ buckets, int half, int nseg, int lb, u32 *__restrict__ SW, u32 *__restrict__ cols, int direct,
-                                                   const u32 *__restrict__ bad_ws, int k0) {
+                                                   const u32 *__restrict__ bad_ws) {
     C25519_PRIO_SIDE();
     __shared__ __attribute__((aligned(16))) u32 S[RC_WORDS], W[RC_WORDS], scratch[RC_WORDS], tot[40];
     // (the roles rotate with the block index: the waves of the ~4 blocks that share a SIMD then play different roles, whose loads differ)
     const int role = __builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 6) + blockIdx.x) & 3), lane = threadIdx.x & 63;
-    const int bid = k0 * nseg + (int)blockIdx.x, k = bid / nseg, seg = bid % nseg;
+    const int bid = (int)blockIdx.x, k = bid / nseg, seg = bid % nseg;
     if (bad_ws && bid == 0 && threadIdx.x == 0 && *bad_ws) atomicOr(cols + MSM_MAX_WIN * 40, 1u);
     const int LB = 1 << lb, b0 = (seg * 64 + lane) * LB;
     const u32 *B = buckets + (u64)k * half * 40;
@@ -216,11 +215,11 @@ __global__ void __launch_bounds__(256) k_reduce_a4(const u32 *__restrict__ bucke
     }
 }
 // level B: one block per window over its nseg <= 64 segment pairs (weight 2^(lb + 6) per segment, of which level A has applied 2^6)
-__global__ void __launch_bounds__(256) k_reduce_b4(const u32 *__restrict__ SW, int nseg, int lb, u32 *__restrict__ cols, int k0) {
+__global__ void __launch_bounds__(256) k_reduce_b4(const u32 *__restrict__ SW, int nseg, int lb, u32 *__restrict__ cols) {
     C25519_PRIO_SIDE();
     __shared__ __attribute__((aligned(16))) u32 S[RC_WORDS], W[RC_WORDS], scratch[RC_WORDS], tot[40];
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int k = k0 + (int)blockIdx.x, mc = rc_coord(role);
+    const int k = (int)blockIdx.x, mc = rc_coord(role);
     rc_put(S, lane, mc, lane < nseg ? rc_global(SW, 2 * ((u64)k * nseg + lane), mc) : rc_ident(mc));
     rc_put(W, lane, mc, lane < nseg ? rc_global(SW, 2 * ((u64)k * nseg + lane) + 1, mc) : rc_ident(mc));
     __syncthreads();
@@ -302,16 +301,14 @@ __global__ void __launch_bounds__(256) k_mid_finish(u32 *__restrict__ cols, cons
 // the bucket reduction of the mid path: level A, then level B with the record's header / publication (a single-segment layout: level A writes the columns, then the flags alone)
 void launch_bucket_reduce_pub(const uint32_t *buckets, const c25519::msm_geom &g, int nseg, uint32_t *SW, uint32_t *out, const uint32_t *blockflags, int nflags, uint32_t *done_cnt,
                               const c25519::reduce_publish &pub, hipStream_t st) {
-    hipLaunchKernelGGL(k_reduce_a4, dim3((unsigned)(g.nwin * nseg)), dim3(256), 0, st, buckets, g.half, nseg, red_lb_log2(g.half), SW, out, nseg == 1 ? 1 : 0, (const u32 *)nullptr, 0);
+    hipLaunchKernelGGL(k_reduce_a4, dim3((unsigned)(g.nwin * nseg)), dim3(256), 0, st, buckets, g.half, nseg, red_lb_log2(g.half), SW, out, nseg == 1 ? 1 : 0, (const u32 *)nullptr);
     if (nseg > 1) hipLaunchKernelGGL(k_reduce_b4pub, dim3((unsigned)g.nwin), dim3(256), 0, st, SW, g.nwin, nseg, red_lb_log2(g.half), out, blockflags, nflags, done_cnt, pub);
     else hipLaunchKernelGGL(k_mid_finish, dim3(1), dim3(256), 0, st, out, blockflags, nflags, pub);
 }
 
 // the bucket reduction of a pass (level A over the segments, level B over the windows) on stream st
-void launch_bucket_reduce4(const uint32_t *buckets, const c25519::msm_geom &g, int nseg, uint32_t *SW, uint32_t *d_slot, const uint32_t *bad_ws, hipStream_t st, int k0, int k1) {
-    if (k1 < 0) k1 = g.nwin;
-    if (k1 <= k0) return;
-    // (bad_ws is folded into the slot by the block of window 0, segment 0: the launch of the first group)
-    hipLaunchKernelGGL(k_reduce_a4, dim3((unsigned)((k1 - k0) * nseg)), dim3(256), 0, st, buckets, g.half, nseg, red_lb_log2(g.half), SW, d_slot, nseg == 1 ? 1 : 0, k0 == 0 ? bad_ws : nullptr, k0);
-    if (nseg > 1) hipLaunchKernelGGL(k_reduce_b4, dim3((unsigned)(k1 - k0)), dim3(256), 0, st, SW, nseg, red_lb_log2(g.half), d_slot, k0);
+void launch_bucket_reduce4(const uint32_t *buckets, const c25519::msm_geom &g, int nseg, uint32_t *SW, uint32_t *d_slot, const uint32_t *bad_ws, hipStream_t st) {
+    // (bad_ws is folded into the slot by the block of window 0, segment 0)
+    hipLaunchKernelGGL(k_reduce_a4, dim3((unsigned)(g.nwin * nseg)), dim3(256), 0, st, buckets, g.half, nseg, red_lb_log2(g.half), SW, d_slot, nseg == 1 ? 1 : 0, bad_ws);
+    if (nseg > 1) hipLaunchKernelGGL(k_reduce_b4, dim3((unsigned)g.nwin), dim3(256), 0, st, SW, nseg, red_lb_log2(g.half), d_slot);
 }

@@ -217,7 +217,7 @@ __global__ void __launch_bounds__(256) k_apply_sign(u32 *__restrict__ pts, u64 d
 // Arithmetic: sc28.h -- radix 2^28, folding with l = 2^252 + c; per signature one 512-bit reduction (95 multiplier instructions)
 // and two 5 x 10 limb products with their reductions (95 each), against ~1200 in the 5 x 52 Montgomery form of rounds 1-2.
 __global__ void __launch_bounds__(256) k_batch_scalars(const uint8_t *__restrict__ hram, const uint8_t *__restrict__ sigs, const uint8_t *__restrict__ z16,
-                                                       u64 n, int signed_z, uint8_t *__restrict__ msm_scalars, u32 *__restrict__ partial, int store_r = 1) {
+                                                       u64 n, int signed_z, uint8_t *__restrict__ msm_scalars, u32 *__restrict__ partial) {
     C25519_PRIO_CHAIN();
     __shared__ u32 red[256][10];
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(256) k_batch_scalars(const uint8_t *__restrict
         u32 out[8];
         sc28_to_words(hz, out);
         store8(msm_scalars, 1 + n + i, out);
-        if (store_r) store8(msm_scalars, 1 + i, zwords);      // (split batches: k_z_expand has written it, and the R half's sort may be reading it)
+        store8(msm_scalars, 1 + i, zwords);
     }
     for (int j = 0; j < 10; j++) red[threadIdx.x][j] = zs.v[j];
     __syncthreads();
@@ -256,7 +256,7 @@ __global__ void __launch_bounds__(256) k_batch_scalars(const uint8_t *__restrict
 }
 
 // msm_scalars[0] = -(sum of the per-block partial sums) mod l: one block, strided sums then a tree
-__global__ void __launch_bounds__(256) k_bsum_finish(const u32 *__restrict__ partial, u32 nblk, uint8_t *__restrict__ msm_scalars, u64 also_at = 0) {
+__global__ void __launch_bounds__(256) k_bsum_finish(const u32 *__restrict__ partial, u32 nblk, uint8_t *__restrict__ msm_scalars) {
     C25519_PRIO_CHAIN();
     __shared__ u32 red[256][10];
     sc28 acc = sc28_zero();
@@ -282,19 +282,8 @@ __global__ void __launch_bounds__(256) k_bsum_finish(const u32 *__restrict__ par
         u32 w[8];
         sc28_to_words(sc28_neg(t), w);
         store8(msm_scalars, 0, w);
-        if (also_at) store8(msm_scalars, also_at, w);         // (split batches: B rides at the end of the A half)
     }
 }
-// msm_scalars[1 + i] = |z_i| zero-extended to 32 bytes (device z-mode: sign-magnitude z16): the R half's scalars, available as soon as the z_i are
-__global__ void __launch_bounds__(256) k_z_expand(const uint8_t *__restrict__ z16, u64 n, uint8_t *__restrict__ msm_scalars) {
-    C25519_PRIO_CHAIN();
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const u32 *zw = reinterpret_cast<const u32 *>(z16) + 4 * i;
-    const u32 w[8] = {zw[0], zw[1], zw[2], zw[3] & 0x7fffffffu, 0, 0, 0, 0};
-    store8(msm_scalars, 1 + i, w);
-}
-
 hipError_t launch_hram(const uint8_t *msgs, const uint64_t *msg_off, uint64_t msgs_len, const uint8_t *sigs, const uint8_t *pks, uint64_t n, uint8_t *hram, uint32_t *flags, hipStream_t st) {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_hram, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, msgs, msg_off, msgs_len, sigs, pks, n, hram, flags);
@@ -410,7 +399,8 @@ static void ztree_host_zs(const uint8_t *hred, const uint8_t *sigs, uint64_t n, 
 typedef std::function<int32_t(int what, hipEvent_t *ready)> verify_stage;
 // (r6) device z-mode, inputs on the device, up to 2^16 signatures.  The ORDER in which the host enqueues the two chains (it needs ~4 us per launch or event, ~80 us
 // for the whole call, and each chain can only run as far as it has been enqueued): 0 = k_hram, the three decompression launches, then tree / z_i / batch scalars;
-// 1 = k_hram and the tree ahead of the decompression; 2 = the decompression ahead of everything.  A/B knob VERIFY_ORDER of the tuning build (-1 = the rule below); verify_pass_enqueue has the numbers.
+// 1 = k_hram and the tree ahead of the decompression; 2 = the decompression ahead of everything (the order of batches beyond 2^18 signatures, where k_hram is not enqueued first).
+// Knob VERIFY_ORDER of the tuning build (-1 = the rule below); verify_pass_enqueue has the numbers.
 // (last) The rule (knob -1): order 1 for key BYTES up to 2^14 signatures -- their one decompression launch of 2n lanes is enqueued in a moment, and behind the three launches
 // of order 0 k_ztree_first started 20 us after the 18 us k_hram of a 4096-signature batch had ended (profiles/r06_timeline_mid_boundary_sizes.txt): 2048 .. 16 384
 // signatures -3 .. -8 us in every pair of runs (profiles/r06_ab_verify_order_small.txt); order 0 with the keys' cached points (level, 16 384 signatures +8 us with order 1).
@@ -437,12 +427,11 @@ __global__ void k_add_point_counters(u32 *__restrict__ d_cnt, const u32 *__restr
 static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len,
                                    const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points, uint64_t n, uint32_t z_mode,
                                    const uint8_t *d_hram_pre, const uint8_t *d_z_pre, const uint32_t *d_pre_flags, const msm_geom &g, uint64_t terms, uint32_t *d_slot, hipEvent_t wait_acc,
-                                   const verify_stage *stage = nullptr, const verify_pre *pre = nullptr, c25519_ctx *split_peer = nullptr, uint32_t *d_slot_b = nullptr) {
+                                   const verify_stage *stage = nullptr, const verify_pre *pre = nullptr) {
     hipStream_t st = ctx->stream;
     const uint64_t m = 2 * n + 1;
     int32_t r;
-    const bool split = split_peer != nullptr && d_slot_b != nullptr && !d_z_pre && !stage && !pre;      // (r6) the batch in two halves: see the end of this function
-    if ((r = ctx_reserve(ctx, ctx->tmp_e, (m + 1) * PTS_BYTES + 256))) return r;      // (+ 1: split batches keep a second copy of B's record behind the keys')
+    if ((r = ctx_reserve(ctx, ctx->tmp_e, (m + 1) * PTS_BYTES + 256))) return r;      // (+ 1: one record of slack)
     // tmp_f: hram (64n) | z16 (16n) | msm scalars (32m) | tree scratch | partial sums
     const unsigned nblk = div_up64(n, 256);
     size_t off = 0;
@@ -471,7 +460,7 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uin
     static const int hram_first_knob = C25519_KNOB("HRAM_FIRST", 1);      // A/B knob: 0 = behind the decompression launches (rounds 1-4)
     // (up to 2^18 signatures: 0.594 -> 0.581 ms at 2^14, 1.034 -> 1.018 at 2^18; at 2^20 the hash kernels then take the compute units ahead of the decompression
     //  and the call is 0.6 % slower: profiles/r05_ab_midrange_streams.txt)
-    const int order = (!stage && !hr && !split) ? verify_order(n, d_pk_points == nullptr) : 0;
+    const int order = (!stage && !hr) ? verify_order(n, d_pk_points == nullptr) : 0;
     const bool hram_first = hram_first_knob && !stage && !hr && n <= (1ull << 18) && order != 2;
     if (hram_first) { hipLaunchKernelGGL(k_hram, dim3(nblk), dim3(256), 0, sa, d_msgs, d_msg_off, msgs_len, d_sigs, d_pks, n, hram, d_cnt + 4, hred); hr = hram; }
     // (r6, late) order 1: the tree and the z_i ahead of the decompression launches as well.  With SHA-512 in the tree (until call 30 of round 6) the chain was the longer
@@ -481,7 +470,7 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uin
     // A batch whose MSM takes the mid path (mid.hip) runs that MSM on THIS stream, right behind its scalars: the digits and the sort need nothing else; the records
     // (main stream) are waited for once, in front of the accumulation, and the sign of z_i is applied to R_i there (msm_mid_enqueue, mid_run).  Before: k_bsum_finish ->
     // 30 us (event, k_apply_sign on the main stream, event) -> k_mid_front at 2^14 signatures, plus an event record between k_zderive and k_batch_scalars.
-    const bool on_chain = !stage && !d_hram_pre && !d_z_pre && !split && ctx->solo && !wait_acc && !pre && verify_on_chain(n, g, false);
+    const bool on_chain = !stage && !d_hram_pre && !d_z_pre && ctx->solo && !wait_acc && !pre && verify_on_chain(n, g, false);
     if (chain_first) {
         if ((r = zchain_enqueue(ctx, sa, hred, d_sigs, n, t0, t1, z16))) return r;
         if (!on_chain) HIPCHK(hipEventRecord(ctx->ev_z, sa));
@@ -523,10 +512,6 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uin
         HIPCHK(hipEventRecord(ring[5], st));
     } else {
         if ((r = prep_A())) return r;
-        if (split) {                                       // B once more, behind the keys' records: the A half is terms n + 1 .. 2n + 1
-            launch_prep_basepoint(d_pts, 2 * n + 1, st);
-            HIPCHK(hipEventRecord(ctx->ev_split, st));
-        }
         if ((r = prep_R())) return r;
     }
     // (A)
@@ -547,43 +532,7 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uin
             hipLaunchKernelGGL(k_apply_sign, dim3(nblk), dim3(256), 0, st, d_pts, (uint64_t)1, zz, n);
         }
     }
-    // (r6) TWO HALVES (round-5 verdict, item 6).  The 2n + 1 terms are two different halves: the R half's scalars are the |z_i| themselves (128 bits: 8 windows) and exist
-    // when k_zderive ends; the A half's are z_i h_i mod l (253 bits) and exist only after k_batch_scalars / k_bsum_finish.  As ONE pass the sort of everything waits for the
-    // last scalar and the accumulation for the whole sort (k_accumulate started 1.56 ms into a 2.61 ms call at 2^20 signatures: profiles/r05_verify_timeline.txt).  As two
-    // passes on the two stream sets -- the R half here, the A half (with B behind it) on the peer context -- the R half's sort and accumulation run while the A half's
-    // scalars and sort are still being made; the accumulations follow each other, each half reduces its own buckets (same layout), and the two column-sum slots are added
-    // before the one identity check (k_record_sum).  Device z-mode, single-pass batches of the bucket pipeline only.
-    // MEASURED AND NOT ADOPTED (profiles/r06_ab_verify_split.txt, bit-exact in the full verify / multi / ffi modules): 2^20 signatures 2.80 against 2.60 ms, 2^19 1.66
-    // against 1.50.  The premise does not hold: the R half cannot accumulate before R is decompressed (1.37 ms into the call: 0.33 ms of key normalisation, then 0.97 ms
-    // of decompression on the main stream), its sort beside that decompression takes 0.53 instead of 0.25 ms, and two accumulations + two reductions cost two ramp-downs.
-    // The arm stays behind VERIFY_SPLIT_MIN of the tuning build (default 0 = never) for one round.
-    if (split) {
-        c25519_ctx *pc = split_peer;
-        hipStream_t pa = pc->aux, ps = pc->stream;
-        // R half: |z_i| right behind k_zderive on the second stream; the sort follows there, the accumulation on the main stream behind the decompression of R
-        // (ev_z was recorded above, BEFORE the expansion: the sign application needs only z16; record it again behind the expansion for the A chain)
-        hipLaunchKernelGGL(k_z_expand, dim3(nblk), dim3(256), 0, sa, zz, n, msc);
-        HIPCHK(hipEventRecord(ctx->ev_z, sa));
-        // A chain on the PEER's second stream: it must not queue behind the R half's long-bucket kernels, which wait for the main stream
-        HIPCHK(hipStreamWaitEvent(pa, ctx->ev_z, 0));
-        hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, pa, hr, d_sigs, zz, n, 1, msc, partial, 0);
-        hipLaunchKernelGGL(k_bsum_finish, dim3(1), dim3(256), 0, pa, partial, nblk, msc, (u64)(2 * n + 1));
-        HIPCHK(hipGetLastError());
-        // the peer's main stream: behind the keys' records and B's second copy (ev_split, recorded by prep below / above) and behind the R half's accumulation (wait_acc)
-        HIPCHK(hipStreamWaitEvent(ps, ctx->ev_split, 0));
-        hipEvent_t *ring_b = pass_ring(owner, pc, 1);
-        HIPCHK(hipEventRecord(ring_b[3], ps));
-        slot_init(d_slot_b, terms, nullptr, ps, g.c);
-        ctx->solo = false; pc->solo = false;
-        if ((r = msm_enqueue(ctx, msc + 32, n, d_pts + (size_t)1 * (PTS_BYTES / 4), g, d_slot, ring, sa, wait_acc))) return r;
-        if ((r = msm_enqueue(pc, msc + 32 * (n + 1), n + 1, d_pts + (size_t)(n + 1) * (PTS_BYTES / 4), g, d_slot_b, ring_b, pa, ctx->ev_acc))) { if (ctx->err.empty()) ctx->err = pc->err; return r; }
-        // join: the caller's stream continues behind the peer's half; the two slots become one
-        HIPCHK(hipEventRecord(pc->ev_in, ps));
-        HIPCHK(hipStreamWaitEvent(st, pc->ev_in, 0));
-        launch_record_sum(d_slot, d_slot, 2, g.nwin, 1, st);
-        HIPCHK(hipGetLastError());
-        return C25519_OK;
-    }
+    // (the batch as two passes on the two stream sets -- the R half, whose scalars exist early, and the A half: measured and not adopted, profiles/r06_ab_verify_split.txt)
     hipLaunchKernelGGL(k_batch_scalars, dim3(nblk), dim3(256), 0, sa, hr, d_sigs, zz, n, z_mode == C25519_Z_DEVICE ? 1 : 0, msc, partial);
     // the basepoint coefficient -sum z_i s_i (batch.rs:240): the per-block partial sums are folded by one more block
     hipLaunchKernelGGL(k_bsum_finish, dim3(1), dim3(256), 0, sa, partial, nblk, msc);
@@ -769,11 +718,8 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
             const uint64_t lo = (p0 + i) * per, m = std::min(per, n - lo);
             c25519_ctx *c = ps.c[(p0 + i) % ps.lanes];
             const verify_stage stage = [&](int what, hipEvent_t *ready) -> int32_t { return (*fetch)(lo, m, what, ready); };
-            // (r6) a single-pass batch of the bucket pipeline in two halves on the two stream sets (verify_pass_enqueue; A/B knob VERIFY_SPLIT_MIN, 0 = never)
-            static const uint64_t split_min = (uint64_t)C25519_KNOB_LL("VERIFY_SPLIT_MIN", 0);      // MEASURED AND NOT ADOPTED (profiles/r06_ab_verify_split.txt): 2.80 against 2.60 ms at 2^20
-            c25519_ctx *split_peer = (passes == 1 && !fetch && split_min && m >= split_min && !msm_mid_serves(2 * m + 1, g, true) && 2 * m + 1 > verify_small_max()) ? ctx_peer(ctx) : nullptr;
             r = verify_pass_enqueue(ctx, c, d_msgs, d_msg_off + lo, msgs_len, d_sigs + lo * 64, d_pks + lo * 32, d_pk_points ? d_pk_points + lo * 160 : nullptr, m, z_mode,
-                                    nullptr, nullptr, nullptr, g, 2 * per + 1, dslot(ctx, i), prev_acc, fetch ? &stage : nullptr, nullptr, split_peer, split_peer ? dslot(ctx, 1) : nullptr);
+                                    nullptr, nullptr, nullptr, g, 2 * per + 1, dslot(ctx, i), prev_acc, fetch ? &stage : nullptr);
             if (r) { ctx->direct_seq = 0; if (ctx->err.empty()) ctx->err = c->err; return r; }
             prev_acc = ps.lanes > 1 ? c->ev_acc : nullptr;
             if (n >= (1ull << 16) && !direct) ctx->coarse_wait = c->ev_acc;

@@ -243,35 +243,25 @@ def test_msm_affine_and_projective_lanes_mixed(eng, orc):
 
 @pytest.mark.parametrize("env", [{}, {"C25519_MSM_PASS_LOG2": "16"}, {"C25519_MSM_PASS_LOG2": "16", "C25519_PASS_LANES": "1"},
                                  {"C25519_MSM_PASS_LOG2": "16", "C25519_PASS_LANES": "3"},
-                                 {"C25519_SORT_SMALL": "1"}, {"C25519_SORT_SMALL": "1", "C25519_MSM_PASS_LOG2": "16"},      # the A/B arms of round 4 stay bit-exact
-                                 {"C25519_REDUCE_COOP": "0"},
                                  {"C25519_SORT_CHUNK_LOCAL_MIN": "2048"},                   # the chunk-local sort at its smallest sizes (one to a few chunks per window)
-                                 # how far the sort of a continuing pass runs ahead of its predecessor's accumulation (0 = not at all, 1 = the partition
-                                 # half, 2 = all of it on a second copy of the lists), with the chunk-local sort on many short passes
-                                 {"C25519_SWEEP_EARLY": "0", "C25519_MSM_PASS_LOG2": "16", "C25519_SORT_CHUNK_LOCAL_MIN": "2048"},
-                                 {"C25519_SWEEP_EARLY": "1", "C25519_MSM_PASS_LOG2": "16", "C25519_SORT_CHUNK_LOCAL_MIN": "2048"},
-                                 {"C25519_SWEEP_EARLY": "2", "C25519_MSM_PASS_LOG2": "16", "C25519_SORT_CHUNK_LOCAL_MIN": "2048"},
-                                 {"C25519_SWEEP_EARLY": "2", "C25519_MSM_PASS_LOG2": "16", "C25519_PASS_LANES": "3"},
+                                 # the partition half of a continuing pass's sort ahead of its predecessor's accumulation, with the chunk-local sort on many short passes
+                                 {"C25519_MSM_PASS_LOG2": "16", "C25519_SORT_CHUNK_LOCAL_MIN": "2048"},
+                                 # four stream sets; the sort behind the normaliser (the profiling order)
+                                 {"C25519_MSM_PASS_LOG2": "16", "C25519_PASS_LANES": "4"}, {"C25519_PROFILE_SERIAL_SORT": "1", "C25519_MSM_PASS_LOG2": "16"},
                                  # the layouts of rounds 1-3 (window width log2 n - 4 throughout, at most 16 bits; 8 buckets per lane in the reduction)
                                  {"C25519_MSM_MIDRANGE_WINDOWS": "0", "C25519_MSM_CMAX": "16", "C25519_RED_LB_MIN": "3"},
                                  {"C25519_MSM_MIDRANGE_WINDOWS": "0", "C25519_SORT_CHUNK_LOCAL_MIN": "2048"},
-                                 # every pass normalises its own points; the 512-thread partition
-                                 {"C25519_PREP_AHEAD": "0", "C25519_MSM_PASS_LOG2": "16"}, {"C25519_SWEEP_THREADS": "512", "C25519_SORT_CHUNK_LOCAL_MIN": "2048"},
-                                 # round 5: single-pass calls in two window groups (bucket order, accumulation and reduction group by group), the sort enqueued
-                                 # ahead of the normaliser.  (Three / four groups, SORT_FIRST=2, PREP_SPLIT, 7-bit small tables lost on two boxes each and left the
-                                 # tuning build in round 6: profiles/r05_ab_window_groups.txt, r05_ab_prep_split.txt, r05_ab_small_path_range.txt are the record.)
-                                 {"C25519_ACC_GROUPS": "2"}, {"C25519_SORT_FIRST": "1"},
+                                 # every pass normalises its own points
+                                 {"C25519_PREP_AHEAD": "0", "C25519_MSM_PASS_LOG2": "16"},
                                  {"C25519_REDUCE_MAIN": "0"}, {"C25519_SMALL_DIRECT": "0"},      # the reduction of a single-pass call on the second stream (rounds 3-4); small calls through their slot
                                  # the small path's range: round 4's (4095 terms), and 5-bit windows far beyond the default boundary
                                  {"C25519_MSM_SMALL_MAX": "4095"}, {"C25519_MSM_SMALL_MAX": "40000", "C25519_MSM_SMALL_C": "5"},
                                  # round 6, the mid path: off (the bucket pipeline from 12 288 terms, as it still serves everything beyond 2^17), the normaliser +
-                                 # k_accumulate arm from 12 288 terms, many small sort slices, up to 2^18 terms; streaming normaliser / sort reads
+                                 # k_accumulate arm from 12 288 terms, many small sort slices, up to 2^18 terms; passes of 2^20 terms
                                  {"C25519_MSM_MID_MAX": "0"}, {"C25519_MID_PROJ_MAX": "0"}, {"C25519_MID_SORT_BLOCKS": "1024", "C25519_MSM_MID_MAX": "262144"},
-                                 {"C25519_PREP_NT": "1", "C25519_SWEEP_NT": "1", "C25519_MSM_PASS_LOG2": "20"},
-                                 # round 6, late: the cap on a bucket lane's list (the first mid path's rule; many lists above it at every size), the over-long
-                                 # lists as a launch of their own, the cooperative gather from the first size of the path
-                                 {"C25519_MID_LONG_TARGET": "0"}, {"C25519_MID_LONG_TARGET": "2048", "C25519_MID_LONG_TARGET_ALWAYS": "1"},
-                                 {"C25519_MID_RAW_FUSED": "0"}, {"C25519_MID_COOP_MIN": "12288"}])
+                                 {"C25519_MSM_PASS_LOG2": "20"},
+                                 # round 6, late: the cap on a bucket lane's list (the first mid path's rule; many lists above it at every size)
+                                 {"C25519_MID_LONG_TARGET": "0"}, {"C25519_MID_LONG_TARGET": "2048", "C25519_MID_LONG_TARGET_ALWAYS": "1"}])
 def test_msm_kernel_variants_in_a_fresh_process(orc, env):
     """The remaining knobs (pass size, number of stream sets) are read once per process: 2^16-term passes make a small input
     run many passes (more than the 16 result slots at the largest size: the slots are reused and the record is summed in
@@ -395,29 +385,6 @@ def test_msm_long_runs_in_a_few_chunks(eng, orc):
     draw = eng.mul_base_batch_t(dx, out_fmt=2)
     st, got = eng.msm_vartime_t(dx, draw, in_fmt=2, out_fmt=0)
     assert st == 0 and got == orc.ed_compress(orc.ed_mul_base(i2b(_sumsq_device(dx))))
-
-
-def test_msm_small_sort_blocks_256_slices(orc):
-    """C25519_SORT_SMALL=1 (round 4's A/B arm: 256-thread partition blocks) at a pass size whose windows have 256 slices -- as many as the block
-    has threads (the slice-start copy-out must loop); fresh process: the knob is read once."""
-    import os, subprocess, sys, textwrap
-    code = textwrap.dedent("""
-        import sys, torch
-        sys.path.insert(0, %r); sys.path.insert(0, %r)
-        import test_gpu_msm as T, curve25519_dalek_amd as pkg
-        from oracle import orc
-        eng = pkg.Engine(0)
-        for n in (2200001, 2625000):
-            g = torch.Generator(device="cuda"); g.manual_seed(4321 + n)
-            dx = torch.randint(0, 256, (n, 32), dtype=torch.uint8, device="cuda", generator=g)
-            dx[:, 31] &= 0x0F
-            draw = eng.mul_base_batch_vartime_t(dx, out_fmt=2)
-            st, got = eng.msm_vartime_t(dx, draw, in_fmt=2, out_fmt=0)
-            assert st == 0 and got == orc.ed_compress(orc.ed_mul_base(T.i2b(T._sumsq_device(dx)))), n
-        print("ok")
-    """) % (os.path.dirname(os.path.abspath(__file__)), os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    r = subprocess.run(util.child_argv(code), env=util.tune_env(C25519_SORT_SMALL="1"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-500:], r.stderr[-2000:])
 
 
 @pytest.mark.parametrize("log2pass,n", [(21, 5898242), (22, 12386305)])
