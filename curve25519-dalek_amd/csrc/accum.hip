@@ -121,7 +121,7 @@ __device__ __forceinline__ void accumulate_body(const u32 *__restrict__ pts, con
 #undef C25519_COOP_ISSUE
     if (!mine) return;
 #if !defined(C25519_ACC_SIGN_SELECT) && defined(__HIP_DEVICE_COMPILE__)
-    acc.X = fe_carry(feW(fe_cond_neg(acc.X, sgn))); acc.T = fe_carry(feW(fe_cond_neg(acc.T, sgn)));      // back to the true sum (tight limbs: p40_store's format)
+    ge_lazy_sign_resolve(acc, sgn);      // back to the true sum (tight limbs: p40_store's format)
 #endif
     p40_store(buckets, gid, acc);
 }

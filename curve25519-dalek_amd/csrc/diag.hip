@@ -2,7 +2,8 @@
 //   * the device self-tests -- K1, the FIELD layer as compiled for the GPU (selftest.h; this unit holds the chained-carry
 //     flavour, finish.hip the ten-column one), and the SCALAR layer (sc28.h: the arithmetic mod l of verify_batch / sign /
 //     per-signature verify) -- raw limbs or words in, canonical bytes out, compared with Python big integers by
-//     tests/test_gpu_field.py at 2^20 random values plus the extremes of every bound class;
+//     tests/test_gpu_field.py at 2^20 random values plus the extremes of every bound class; and K2, the POINT formulas between
+//     them (selftest_point.h, the same two flavours; tests/test_gpu_point.py);
 //   * the instruction-rate probes behind c25519_microbench (bench.py's live v_mad_u64_u32 peak, tools/probes.py).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -11,6 +12,7 @@
 #include "devio.h"
 #include "kernels.h"
 #include "selftest.h"
+#include "selftest_point.h"
 #include "fe26x.h"
 #include "sc28.h"
 #include "fe9_probe.h"
@@ -377,6 +379,12 @@ hipError_t launch_selftest_c1(int op, const uint32_t *a, const uint32_t *b, uint
     return hipGetLastError();
 }
 
+hipError_t launch_selftest_point_c1(int op, const uint32_t *p, const uint32_t *q, const uint32_t *aux, uint64_t n, uint8_t *out, hipStream_t st) {   // chained-carry unit
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_selftest_point<1>, dim3(div_up(n, 256)), dim3(256), 0, st, op, p, q, aux, n, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_probe(int which, uint32_t *out, int iters, unsigned grid, hipStream_t st) {
     switch (which) {
     case 0: hipLaunchKernelGGL(k_probe_mad, dim3(grid), dim3(256), 0, st, out, iters, 12345u); break;
@@ -442,7 +450,7 @@ using namespace c25519;
 // field self-test: raw limbs (n x 10 u32, HOST pointers; b may be NULL for the unary ops) -> n x 32 canonical bytes
 EXPORT int32_t c25519_selftest_field(c25519_ctx *ctx, int op, int chain, const uint32_t *a_limbs, const uint32_t *b_limbs, uint64_t n, uint8_t *out) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (op < 0 || op > 11 || (chain != 0 && chain != 1)) { ctx->err = "selftest_field: bad op / chain"; return -(int32_t)hipErrorInvalidValue; }
+    if (op < 0 || op > 16 || (chain != 0 && chain != 1)) { ctx->err = "selftest_field: bad op / chain"; return -(int32_t)hipErrorInvalidValue; }
     if (n == 0) return C25519_OK;
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 40)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * 40)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 32))) return r;
@@ -452,6 +460,26 @@ EXPORT int32_t c25519_selftest_field(c25519_ctx *ctx, int op, int chain, const u
     if (chain) HIPCHK(launch_selftest_c1(op, (const uint32_t *)ctx->tmp_a.p, db, n, (uint8_t *)ctx->tmp_c.p, ctx->stream));
     else HIPCHK(launch_selftest_c0(op, (const uint32_t *)ctx->tmp_a.p, db, n, (uint8_t *)ctx->tmp_c.p, ctx->stream));
     HIPCHK(hipMemcpyAsync(out, ctx->tmp_c.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return C25519_OK;
+}
+
+// point self-test: raw limbs (p: n x 40 u32 = X Y Z T; q: n x 40 u32, may be NULL; aux: n u32, may be NULL; HOST pointers) -> n x 128 bytes: canonical X Y Z T
+EXPORT int32_t c25519_selftest_point(c25519_ctx *ctx, int op, int chain, const uint32_t *p_limbs, const uint32_t *q_limbs, const uint32_t *aux, uint64_t n, uint8_t *out) {
+    HIPCHK(hipSetDevice(ctx->device));
+    if (op < 0 || op >= SELFTEST_POINT_OPS || (chain != 0 && chain != 1)) { ctx->err = "selftest_point: bad op / chain"; return -(int32_t)hipErrorInvalidValue; }
+    if (n == 0) return C25519_OK;
+    int32_t r;
+    // (tmp_b: q, and aux behind it)
+    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 160)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * 164)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 128))) return r;
+    HIPCHK(hipMemcpyAsync(ctx->tmp_a.p, p_limbs, n * 160, hipMemcpyHostToDevice, ctx->stream));
+    if (q_limbs) HIPCHK(hipMemcpyAsync(ctx->tmp_b.p, q_limbs, n * 160, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t *d_aux = (uint32_t *)((uint8_t *)ctx->tmp_b.p + n * 160);
+    if (aux) HIPCHK(hipMemcpyAsync(d_aux, aux, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t *dq = q_limbs ? (const uint32_t *)ctx->tmp_b.p : nullptr, *da = aux ? d_aux : nullptr;
+    if (chain) HIPCHK(launch_selftest_point_c1(op, (const uint32_t *)ctx->tmp_a.p, dq, da, n, (uint8_t *)ctx->tmp_c.p, ctx->stream));
+    else HIPCHK(launch_selftest_point_c0(op, (const uint32_t *)ctx->tmp_a.p, dq, da, n, (uint8_t *)ctx->tmp_c.p, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, ctx->tmp_c.p, n * 128, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return C25519_OK;
 }

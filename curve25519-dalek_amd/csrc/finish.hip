@@ -8,6 +8,7 @@
 #include "devio.h"
 #include "kernels.h"
 #include "selftest.h"
+#include "selftest_point.h"
 #include "capi_util.h"
 
 namespace c25519 {
@@ -127,6 +128,12 @@ __global__ void __launch_bounds__(256) k_raw_to_p32(const uint8_t *__restrict__ 
 hipError_t launch_selftest_c0(int op, const uint32_t *a, const uint32_t *b, uint64_t n, uint8_t *out, hipStream_t st) {   // ten-column unit
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_selftest_field<0>, dim3(div_up(n, 256)), dim3(256), 0, st, op, a, b, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_selftest_point_c0(int op, const uint32_t *p, const uint32_t *q, const uint32_t *aux, uint64_t n, uint8_t *out, hipStream_t st) {   // ten-column unit
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_selftest_point<0>, dim3(div_up(n, 256)), dim3(256), 0, st, op, p, q, aux, n, out);
     return hipGetLastError();
 }
 

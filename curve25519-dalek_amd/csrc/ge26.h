@@ -143,6 +143,13 @@ C25519_HD ge_p3 ge_madd_lazy_p3(const ge_p3 &p, const ge_aniels &q, u32 flip) {
     r.T = fe_mul(feW(X), Y);
     return r;
 }
+// The end of a lazily signed chain: sgn = all ones while the stored point is MINUS the sum -- back to the true sum, tight limbs (p40_store's format).  Shared by
+// accum.hip accumulate_body and the chain of the point self-test (selftest_point.h op 12), and host code like ge_madd_lazy_p3 so that tests/host/fe26_host.cpp reaches
+// it.  (The A/B arm C25519_MID_SIGN_LAZY of mid.hip mid_acc_body keeps the same two statements written out: through this function the compiler schedules two
+// instructions of that kernel in another order.)
+C25519_HD void ge_lazy_sign_resolve(ge_p3 &acc, u32 sgn) {
+    acc.X = fe_carry(feW(fe_cond_neg(acc.X, sgn))); acc.T = fe_carry(feW(fe_cond_neg(acc.T, sgn)));
+}
 
 // (neg ? -Q : Q) as an extended point, for the FIRST addition of a chain (identity + Q): with (y+x, y-x, 2dxy) at hand,
 // (X : Y : Z : T) = (2x : 2y : 2 : 2xy) is (y+x) - (y-x), (y+x) + (y-x), 2 and 2dxy / d -- one multiplication by the

@@ -164,6 +164,7 @@ _SIGS = {
     "c25519_microbench": (C.c_double, [_vp, C.c_int, C.c_int]),
     "c25519_selftest_field": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _u64, _vp]),
     "c25519_selftest_scalar": (_i32, [_vp, C.c_int, _vp, _vp, _u64, _vp]),
+    "c25519_selftest_point": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _u64, _vp]),
     "c25519_debug_workspace_count": (_i32, [_vp]),
     "c25519_debug_workspace_info": (_i32, [_vp, C.c_int, _vp, _vp]),
     "c25519_debug_workspace_read": (_i32, [_vp, C.c_int, _u64, _u64, _vp]),
@@ -288,6 +289,17 @@ class Engine:
         out = np.empty((n, 32), dtype=np.uint8)
         self._bind_stream()
         self._chk(self.lib.c25519_selftest_field(self.ctx, op, chain, a.ctypes.data, b.ctypes.data if b is not None else None, n, out.ctypes.data))
+        return out
+
+    def selftest_point(self, op, p, q=None, aux=None, chain=0):
+        """one point formula per row on the GPU: (n, 40) uint32 limbs X Y Z T, q (n, 40) and aux (n,) as the op takes them -> (n, 128) canonical X Y Z T (c25519_selftest_point)"""
+        p = np.ascontiguousarray(p, dtype=np.uint32).reshape(-1, 40); n = p.shape[0]
+        q = None if q is None else np.ascontiguousarray(q, dtype=np.uint32).reshape(-1, 40)
+        aux = None if aux is None else np.ascontiguousarray(aux, dtype=np.uint32).reshape(-1)
+        assert (q is None or q.shape[0] == n) and (aux is None or aux.shape[0] == n)
+        out = np.empty((n, 128), dtype=np.uint8)
+        self._bind_stream()
+        self._chk(self.lib.c25519_selftest_point(self.ctx, op, chain, p.ctypes.data, q.ctypes.data if q is not None else None, aux.ctypes.data if aux is not None else None, n, out.ctypes.data))
         return out
 
     def selftest_scalar(self, op, a_words, b_words=None):

@@ -568,9 +568,24 @@ double c25519_microbench(c25519_ctx *ctx, int which, int iters);
  * any magnitudes the operation's bound class admits, csrc/fe26.h); out: n x 32.  op: 0 a*b (a wide, b loose), 1 a^2
  * (loose), 2 1/a, 3 canonical encoding of a (wide), 4 a^((p-5)/8), 5 a-b (both loose), 6 weak reduction of a,
  * 7 (a-b)*(a+b) (both tight); 8-11 the lockstep multiplier of the bucket accumulation (csrc/fe26x.h; a wide, b loose):
- * 8 a*b and 9 b^2 out of one group of three products, 10 a*b and 11 b^2 out of one group of four.  Pins the device code
- * generation against big integers (field.rs:552-642). */
+ * 8 a*b and 9 b^2 out of one group of three products, 10 a*b and 11 b^2 out of one group of four; 12, 13 a*b out of the
+ * first / the second slot of a lockstep pair (csrc/mid_long.h); 14 b[0] ? -a : a (a tight; b[0] = 0 or ~0: fe_cond_neg),
+ * 15 a+b (both loose, fe_add_w), 16 2a+b (both tight, fe_add_lt).  Pins the device code generation against big integers
+ * (field.rs:552-642). */
 int32_t c25519_selftest_field(c25519_ctx *ctx, int op, int chain, const uint32_t *a_limbs, const uint32_t *b_limbs, uint64_t n, uint8_t *out);
+/* Device point self-test: ONE point formula of csrc/ge26.h / fe26x.h / mid_long.h per row on the GPU, in either translation-unit
+ * flavour (chain as above), on raw limbs: p_limbs n x 40 u32 = X Y Z T, q_limbs n x 40 u32 (the second operand in the form the op
+ * names; may be NULL), aux n u32 (sign / flip / count; may be NULL) -- HOST pointers, tight limbs (csrc/fe26.h); out: n x 128 =
+ * the canonical encodings of X Y Z T.  op: 0 2p; 1 2^aux p (aux 1..8); 2 p +- q through aniels_words_cneg + ge_madd (q = 24
+ * canonical words y+x, y-x, 2dxy); 3 / 4 ge_madd_signed_p3 and its lockstep form (q = y+x, y-x, 2dxy limbs; aux & 1: subtract);
+ * 5 / 6 ge_madd_lazy_p3 and its lockstep form (aux != 0: p changes sides first); 7 ge_from_aniels_signed; 8 p +- q through
+ * ge_cached_cneg + ge_add_cached (q a point); 9 ge_add; 10 / 11 the signed and the lazy lockstep addition of a projective Niels
+ * record (q = Y+X, Y-X, Z, 2dT); 12 sixteen lazy lockstep additions of q with the signs in bits 0..15 of aux, then the sign
+ * resolution, as the bucket accumulation chains them; 13 -p; 14 byte 0 = ge_eq(p,q) | ge_is_identity(p) << 1 | ris_eq(p,q) << 2.
+ * Compared coordinate by coordinate with big-integer formulas (curve_models.rs:365-494, edwards.rs:528-535, 1370-1380) by
+ * tests/test_gpu_point.py. */
+int32_t c25519_selftest_point(c25519_ctx *ctx, int op, int chain, const uint32_t *p_limbs /* n x 40: X Y Z T */, const uint32_t *q_limbs /* n x 40, may be NULL */,
+                              const uint32_t *aux /* n, may be NULL */, uint64_t n, uint8_t *out /* n x 128: canonical X Y Z T */);
 /* The same for the device SCALAR arithmetic mod l (csrc/sc28.h: ten 28-bit limbs, reduction by folding with l = 2^252 + c),
  * which replaces Scalar52 (u64/scalar.rs:66-320) inside the verify_batch / sign / per-signature-verify kernels.
  * a_words / b_words: n x 16 u32 per operand (HOST pointers; b may be NULL for the unary ops); out: n x 32 bytes.

@@ -79,6 +79,24 @@ void h_ge_from_aniels_signed(const uint8_t *q, int neg, uint8_t *o) {
 void h_ge_add_cached_signed(const uint8_t *a, const uint8_t *q, int neg, uint8_t *o) {
     pstore(o, ge_p1p1_to_p3(ge_add_cached(pload(a), ge_cached_cneg(ge_p3_to_cached(pload(q)), neg != 0))));
 }
+// the lazily signed addition of the bucket accumulation (ge_madd_lazy_p3: the host form of fe26x.h ge_madd_lazy_p3_lockstep) on RAW limbs, so that a chain keeps the
+// limbs one addition hands the next: p and o are 40 u32 = X Y Z T (tight), q an extended point with Z = 1 as 4 x 32 bytes, flip != 0: p changes sides first
+static ge_p3 pload_limbs(const uint32_t *p) { ge_p3 r; for (int i = 0; i < 10; i++) { r.X.v[i] = p[i]; r.Y.v[i] = p[10 + i]; r.Z.v[i] = p[20 + i]; r.T.v[i] = p[30 + i]; } return r; }
+static void pstore_limbs(uint32_t *o, const ge_p3 &r) { for (int i = 0; i < 10; i++) { o[i] = r.X.v[i]; o[10 + i] = r.Y.v[i]; o[20 + i] = r.Z.v[i]; o[30 + i] = r.T.v[i]; } }
+void h_ge_madd_lazy(const uint32_t *p, const uint8_t *q, uint32_t flip, uint32_t *o) {
+    ge_p3 Q = pload(q);
+    ge_aniels A;
+    A.ypx = fe_carry(fe_add(Q.Y, Q.X)); A.ymx = fe_carry(fe_sub(Q.Y, Q.X)); A.xy2d = fe_mul(Q.T, fe_d2());
+    pstore_limbs(o, ge_madd_lazy_p3(pload_limbs(p), A, flip ? ~0u : 0u));
+}
+// the end of such a chain (ge_lazy_sign_resolve: what accum.hip and mid.hip run after their loops)
+void h_ge_lazy_sign_resolve(const uint32_t *p, uint32_t sgn, uint32_t *o) { ge_p3 a = pload_limbs(p); ge_lazy_sign_resolve(a, sgn ? ~0u : 0u); pstore_limbs(o, a); }
+// its limb-level helpers, raw limbs in and out: a tight, m = 0 or ~0; a and b loose
+void h_fe_cond_neg_limbs(const uint32_t *a, uint32_t m, uint32_t *o) { feT A; for (int i = 0; i < 10; i++) A.v[i] = a[i]; const feL r = fe_cond_neg(A, m); for (int i = 0; i < 10; i++) o[i] = r.v[i]; }
+void h_fe_add_w_limbs(const uint32_t *a, const uint32_t *b, uint32_t *o) {
+    feL A, B; for (int i = 0; i < 10; i++) { A.v[i] = a[i]; B.v[i] = b[i]; }
+    const feW r = fe_add_w(A, B); for (int i = 0; i < 10; i++) o[i] = r.v[i];
+}
 // X25519 ladder exactly as the kernel runs it (montgomery.rs:183-211), s = already-clamped scalar
 void h_x25519_ladder(const uint8_t *s, const uint8_t *u, uint8_t *o) {
     feT au = load(u); mont_pp x0, x1; x0.U = fe_one(); x0.W = fe_zero(); x1.U = au; x1.W = fe_one();

@@ -73,7 +73,7 @@ TABLE = [
     (r"k_nonzero32", SECRET, "reads the shared secrets (was_contributory)", {}),
     (r"k_double_compress<16>", PUBLIC, "double_and_compress_batch takes public points (no secret-taking entry point reaches it)", {}),
     (r"k_prep_small_verify", PUBLIC, "verify_batch: signatures and keys", {}),
-    (r"k_selftest_(field<\d>|scalar)", PUBLIC, "diagnostics: device self-tests on test vectors", {}),
+    (r"k_selftest_(field<\d>|point<\d>|scalar)", PUBLIC, "diagnostics: device self-tests on test vectors", {}),
     (r"k_probe_\w+(<.*>)?", PUBLIC, "diagnostics: instruction-rate probes, no inputs", {}),
     # ---- the newest files: whole-kernel tests of their own stay the authority ----
     (r"k_mont_(mul|mul_bits|to_edwards_prep|to_edwards<\d, (true|false)>)", SECRET_LOOP_ONLY, "test_ct_isa_montgomery (whole kernel)", {}),

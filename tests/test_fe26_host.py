@@ -186,6 +186,67 @@ def test_point_formulas_vs_oracle(host, orc):
     assert call(host, "h_ge_compress", acc_h) == orc.ed_compress(acc_o)
 
 
+def test_lazy_sign_chain_and_its_helpers(host, orc):
+    """The lazily signed addition of the bucket accumulation (ge26.h ge_madd_lazy_p3, the host form of fe26x.h ge_madd_lazy_p3_lockstep) chained on RAW limbs with
+    alternating and random flips against the oracle's ed_add / ed_sub, the sign resolution behind it, and the two limb-level helpers -- fe_cond_neg, fe_add_w -- at the
+    extremes of their classes, all under C25519_CHECK_BOUNDS."""
+    rng = random.Random(106)
+    A10, A40 = C.c_uint32 * 10, C.c_uint32 * 40
+
+    def canon(l40):
+        limbs = [int.from_bytes(l40[8 * i:8 * i + 8], "little") for i in range(5)]
+        return sum(v << (51 * i) for i, v in enumerate(limbs)) % P
+
+    def limbs_of(v):
+        return [(v >> POS[i]) & ((1 << (25 if i & 1 else 26)) - 1) for i in range(10)]
+
+    def as_bytes(l40):  # 40 raw limbs -> 4 x 32 canonical bytes
+        return b"".join(i2b(limbs_val(l40[10 * k:10 * k + 10]) % P) for k in range(4))
+
+    def lazy(acc, qh, flip):
+        o = A40()
+        host.h_ge_madd_lazy(A40(*acc), qh, C.c_uint32(flip), o)
+        return list(o)
+
+    def resolve(acc, sgn):
+        o = A40()
+        host.h_ge_lazy_sign_resolve(A40(*acc), C.c_uint32(sgn), o)
+        return list(o)
+
+    pts = [orc.ed_mul_base(i2b(rng.randrange(L))) for _ in range(4)]
+    for start in pts[:2]:
+        for q in pts[2:]:
+            q = orc.ed_decompress(orc.ed_compress(q))                                   # affine copy, Z = 1
+            qh = b"".join(i2b(canon(q[40 * i:40 * i + 40])) for i in range(4))
+            for signs in ([k & 1 for k in range(24)], [1 - (k & 1) for k in range(24)], [0] * 6, [1] * 6, [rng.getrandbits(1) for _ in range(40)]):
+                acc = sum((limbs_of(canon(start[40 * i:40 * i + 40])) for i in range(4)), [])
+                acc_o, sgn = start, 0
+                for me in signs:
+                    nxt = lazy(acc, qh, me ^ sgn)
+                    # one step is madd(flip ? -acc : acc, q): the stored point is MINUS the running sum while the latest sign was minus
+                    assert call(host, "h_ge_compress", as_bytes(nxt)) == call(host, "h_ge_compress", call(host, "h_ge_madd_signed", as_bytes(resolve(acc, me ^ sgn)), qh, C.c_int(0), out=128))
+                    acc, sgn = nxt, me
+                    acc_o = orc.ed_sub(acc_o, q) if me else orc.ed_add(acc_o, q)
+                    assert all(v <= (T_ODD if i & 1 else T_EVEN) for i, v in enumerate(acc))
+                    assert call(host, "h_ge_compress", as_bytes(resolve(acc, sgn))) == orc.ed_compress(acc_o)
+    # fe_cond_neg: a tight -> a, or 2p - a limb by limb (loose); fe_add_w: loose + loose -> wide
+    two_p = [0x7ffffda] + [0x3fffffe if i & 1 else 0x7fffffe for i in range(1, 10)]
+    edge_t = [[0] * 10, [T_ODD if i & 1 else T_EVEN for i in range(10)], limbs_of(P), limbs_of(P - 1), limbs_of(1)]
+    edge_l = [[0] * 10, [L_ODD if i & 1 else L_EVEN for i in range(10)]]
+    for it in range(400):
+        a = edge_t[it] if it < len(edge_t) else rand_limbs(rng, T_EVEN, T_ODD, it % 2 == 0)
+        for m in (0, 0xFFFFFFFF):
+            o = A10(); host.h_fe_cond_neg_limbs(A10(*a), C.c_uint32(m), o)
+            assert list(o) == ([t - v for t, v in zip(two_p, a)] if m else a)
+            assert all(v <= (L_ODD if i & 1 else L_EVEN) for i, v in enumerate(o))
+            assert limbs_val(list(o)) % P == (-limbs_val(a) if m else limbs_val(a)) % P
+        x = edge_l[it % 2] if it < 4 else rand_limbs(rng, L_EVEN, L_ODD, it % 2 == 0)
+        y = edge_l[(it // 2) % 2] if it < 4 else rand_limbs(rng, L_EVEN, L_ODD, it % 3 == 0)
+        o = A10(); host.h_fe_add_w_limbs(A10(*x), A10(*y), o)
+        assert list(o) == [u + v for u, v in zip(x, y)] and all(v <= (W_ODD if i & 1 else W_EVEN) for i, v in enumerate(o))
+        assert limbs_val(list(o)) % P == (limbs_val(x) + limbs_val(y)) % P
+
+
 def test_ladder_vs_oracle(host, orc, golden):
     rng = random.Random(104)
     cases = [(golden.bytes("x25519_tests.rs", "input_scalar", fn="rfc7748_ladder_test1_vectorset1"),

@@ -57,8 +57,15 @@ st, r = e.msm_vartime(big, bp); assert st == 0; h.update(r)
 rng = np.random.default_rng(9)
 a = rng.integers(0, 1 << 26, size=(4096, 10), dtype=np.uint64).astype(np.uint32); a[:, 1::2] >>= 1
 for chain in (0, 1):
-    for op in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11):
+    for op in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15, 16):
         h.update(e.selftest_field(op, a, a[::-1].copy(), chain).tobytes())
+    m = a[::-1].copy(); m[:, 0] = np.where(m[:, 0] & 1, 0xFFFFFFFF, 0)          # op 14, fe_cond_neg: its mask is b's first word, 0 or ~0
+    h.update(e.selftest_field(14, a, m, chain).tobytes())
+    # the point formulas (selftest_point.h): p and q from the same reduced limbs (as the words of op 2 they stay below 2^249: canonical), every op, signs / flips /
+    # doubling counts from aux
+    p4 = a.reshape(-1, 40); q4 = a[::-1].copy().reshape(-1, 40); aux = (np.arange(p4.shape[0]) & 7).astype(np.uint32) + 1
+    for op in range(15):
+        h.update(e.selftest_point(op, p4, q4, aux * 0x1111 if op == 12 else aux, chain).tobytes())
 print("DIGEST", h.hexdigest())
 '''
 

@@ -114,3 +114,37 @@ def test_fe_invert_pow_sub_chains(eng, chain):
     tb[:64] = tb[:64][::-1].copy()
     xa, xb = values(ta), values(tb)
     assert np.array_equal(eng.selftest_field(7, ta, tb, chain), enc([(x - y) * (x + y) for x, y in zip(xa, xb)]))   # (T - T) * (T + T)
+
+
+@pytest.mark.parametrize("chain", [0, 1])
+def test_lockstep_pair_and_lazy_sign_helpers(eng, chain):
+    """what the lazily signed additions and the mid path's additions are made of (fe26x.h, mid_long.h), primitive by primitive: fe_mul_chain_n<2> with the wide
+    operand in either slot, fe_cond_neg (2p - a limb by limb behind a lane mask), fe_add_w (loose + loose -> wide) and fe_add_lt (2 tight + tight -> loose), each at the
+    extremes of its operands' classes"""
+    rng = np.random.default_rng(2900 + chain)
+    n = 1 << 18
+    top = lambda e, o: np.array([[e if i % 2 == 0 else o for i in range(10)]], np.uint32)
+    a = with_edges(rng, n, W_EVEN, W_ODD); b = with_edges(rng, n, L_EVEN, L_ODD)
+    b[:64] = b[:64][::-1].copy()
+    a[64:320] = top(W_EVEN, W_ODD); b[64:320] = top(L_EVEN, L_ODD)                                  # all-maximal operands
+    va, vb = values(a), values(b)
+    ab = enc([x * y for x, y in zip(va, vb)])
+    assert np.array_equal(eng.selftest_field(12, a, b, chain), ab)
+    assert np.array_equal(eng.selftest_field(13, a, b, chain), ab)
+    lb = with_edges(rng, n, L_EVEN, L_ODD)
+    lb[64:320] = top(L_EVEN, L_ODD)
+    assert np.array_equal(eng.selftest_field(15, b, lb, chain), enc([x + y for x, y in zip(vb, values(lb))]))          # loose + loose -> wide
+    ta = with_edges(rng, n, T_EVEN, T_ODD); tb = with_edges(rng, n, T_EVEN, T_ODD)
+    tb[:64] = tb[:64][::-1].copy()
+    ta[64:320] = top(T_EVEN, T_ODD); tb[64:320] = top(T_EVEN, T_ODD)
+    xa, xb = values(ta), values(tb)
+    assert np.array_equal(eng.selftest_field(16, ta, tb, chain), enc([2 * x + y for x, y in zip(xa, xb)]))          # 2 tight + tight -> loose
+    # fe_cond_neg: the mask is the first word of b -- all lanes keep, all lanes negate, and lanes of one wave that differ
+    keep, negd = enc(xa), enc([-x for x in xa])
+    m = np.zeros((n, 10), dtype=np.uint32)
+    assert np.array_equal(eng.selftest_field(14, ta, m, chain), keep)
+    m[:, 0] = 0xFFFFFFFF
+    assert np.array_equal(eng.selftest_field(14, ta, m, chain), negd)
+    pick = rng.integers(0, 2, size=n).astype(bool)
+    m[:, 0] = np.where(pick, 0xFFFFFFFF, 0).astype(np.uint32)
+    assert np.array_equal(eng.selftest_field(14, ta, m, chain), np.where(pick[:, None], negd, keep))
