@@ -353,12 +353,12 @@ static uint32_t mid_pick_cap(uint64_t n, const msm_geom &g, uint32_t upper, bool
     return upper;
 }
 
-// The whole pass: digits (+ records), sort, accumulation, reduction; column sums (and, hdr != 0, the record header) to d_slot -- or, ctx->direct_seq != 0, the
+// The whole pass: digits (+ records), sort, accumulation, reduction; column sums (and, hdr != 0, the record header) to d_slot -- or, call.seq != 0, the
 // record published into the context's page-locked host slot.  src_fmt 0: raw 160-byte points at `points`; 1: affine Niels records at `points` (a decompression made them).
 // hdr 0: the slot was initialised by k_slot_init and carries counters of its own (verify_batch); 1: this pass writes the header (MSM).
 // ring (may be null): [0] / [1] bracket k_mid_acc, [2] end of the pass.
-int32_t msm_mid_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const void *points, int src_fmt, uint64_t n, const msm_geom &g_in, uint32_t *d_slot, int hdr, uint64_t terms, hipEvent_t *ring,
-                        const mid_run *run) {
+int32_t msm_mid_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const void *points, int src_fmt, uint64_t n, const msm_geom &g_in, uint32_t *d_slot, int hdr,
+                        uint64_t terms, hipEvent_t *ring, const mid_run *run) {
     // The cap beyond which a list leaves the bucket lanes for k_mid_long: max(48, 3 x mean) here (the bucket pipeline: max(192, 2.5 x mean), set for passes of millions of
     // terms).  A mid-size call is as long as its longest list: verify_batch of 2^15 signatures with 15-bit windows puts the top 8 bits of the 128-bit z_i into 256 buckets
     // of ~128 entries each -- just under 192 -- and k_accumulate walked them for 368 us where the call of 2^16 signatures (256 entries each: over the cap) took 85
@@ -456,12 +456,10 @@ int32_t msm_mid_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const void *p
     if (ring) { HIPCHK(hipEventRecord(ctx->ev_acc, st)); HIPCHK(hipEventRecord(ring[1], st)); }
     reduce_publish pub = {0, nullptr, 0, (uint32_t)terms, (uint32_t)(terms >> 32), (uint32_t)g.c, hdr, hdr ? nullptr : slot_flags(d_slot)};
     uint32_t *out = d_slot;
-    if (ctx->direct_seq) {
-        out = ctx->hd_msm + (size_t)C25519_MAX_SLOTS * C25519_SLOT_U32;
-        pub.on = 1; pub.host_flag = ctx->hd_msm + (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32; pub.seq = ctx->direct_seq;
-        static const int lose_every = C25519_KNOB("FAULT_LOSE_PUBLICATION", 0);      // (tuning build only: small.hip has the note)
-        const uint64_t nth = ++ctx->counters[C25519_CTR_PUBLISH_DIRECT];
-        if (lose_every > 0 && nth % (uint64_t)(lose_every > 0 ? lose_every : 1) == 0) pub.seq ^= 0x40000000u;
+    if (call.seq) {
+        const publish_target pt = publish_arm(ctx, call.seq);
+        out = pt.rec;
+        pub.on = 1; pub.host_flag = pt.word; pub.seq = pt.seq;
     }
     launch_bucket_reduce_pub(buckets, g, nseg, SW, out, blockflags, (int)nfront, zw + 2, pub, st);
     HIPCHK(hipGetLastError());

@@ -476,15 +476,20 @@ static_assert(C25519_SLOT_U32 == MSM_MAX_WIN * 40 + 16, "slot layout");
 // set: two accumulations side by side only share the multipliers, while a sort beside an accumulation is free.
 // cont: the accumulation starts from the bucket sums the previous pass on this workspace left (no reduction happened in between);
 // reduce: the buckets are reduced into d_slot now (the last pass of a stream set; always, for the single-pass callers)
-int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_plan &pl, const uint32_t *d_pts, uint32_t *d_slot, hipEvent_t *ring, hipEvent_t wait_acc, bool cont, bool reduce,
+// what a caller put on sort_stream (the sort's lists; verify_batch: the batch scalars) comes first: the main stream continues once it exists
+static int32_t sort_stream_join(c25519_ctx *ctx, hipStream_t sort_stream) {
+    if (!sort_stream || sort_stream == ctx->stream) return C25519_OK;
+    HIPCHK(hipEventRecord(ctx->ev_sort, sort_stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sort, 0));
+    return C25519_OK;
+}
+int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_call &call, const msm_plan &pl, const uint32_t *d_pts, uint32_t *d_slot, hipEvent_t *ring, hipEvent_t wait_acc, bool cont, bool reduce,
                         const uint32_t *d_bad_sticky) {
     const msm_geom &g = pl.g;
     // (k_accumulate's gathers address a record by a 32-bit byte offset from the pass's base: 2^25 records of 128 bytes.  The sorts' entries hold 23- / 24-bit ids.)
     if (pl.n > (1ull << 25)) return bad_arg(ctx, "msm: internal error (a pass of more than 2^25 records)");
-    if (pl.sort_stream && pl.sort_stream != ctx->stream) {                // join: the main stream continues once the lists exist
-        HIPCHK(hipEventRecord(ctx->ev_sort, pl.sort_stream));
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_sort, 0));
-    }
+    int32_t r = sort_stream_join(ctx, pl.sort_stream);
+    if (r) return r;
     hipStream_t st = ctx->stream;
     if (wait_acc) HIPCHK(hipStreamWaitEvent(st, wait_acc, 0));
     // long buckets are independent of k_accumulate (which skips them): fold them on the second stream meanwhile
@@ -502,7 +507,7 @@ int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_plan &pl, const uint32_t *d_p
     // of every single-pass call.  The long-bucket kernels stay on the second stream (they run beside the accumulation); the main stream waits for them
     // before the reduction -- long since finished.
     static const int reduce_main = C25519_KNOB("REDUCE_MAIN", 1);       // A/B knob: 0 = always on the second stream (rounds 3-4)
-    const bool red_main = reduce_main && ctx->solo && reduce && !cont && !wait_acc;
+    const bool red_main = reduce_main && call.solo && reduce && !cont && !wait_acc;
     // (one launch over all windows: accumulating and reducing a single-pass call in window groups was measured and not adopted, profiles/r05_ab_window_groups.txt)
     ctx->kname[0] = launch_accumulate(d_pts, pl.sorted, pl.base, pl.perm, (uint64_t)g.nwin * g.half, pl.n, g, pl.buckets, cont ? 1 : 0, st);
     HIPCHK(hipEventRecord(ctx->ev_acc, st));
@@ -532,43 +537,36 @@ int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_plan &pl, const uint32_t *d_p
 }
 // A pass of at most msm_small_max() terms: no sort, no buckets -- small.hip's two launches on the main stream, after whatever the caller
 // put on sort_stream (verify_batch: the batch scalars) and after wait_acc.  src_fmt: 0 raw 160-byte points, 1 affine Niels records.
-static int32_t msm_small_pass(c25519_ctx *ctx, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const msm_geom &g, uint32_t *d_slot, hipEvent_t *ring,
-                              hipStream_t sort_stream, hipEvent_t wait_acc) {
+static int32_t msm_small_pass(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const msm_geom &g, uint32_t *d_slot,
+                              hipEvent_t *ring, hipStream_t sort_stream, hipEvent_t wait_acc) {
     hipStream_t st = ctx->stream;
-    if (sort_stream && sort_stream != st) {
-        HIPCHK(hipEventRecord(ctx->ev_sort, sort_stream));
-        HIPCHK(hipStreamWaitEvent(st, ctx->ev_sort, 0));
-    }
+    int32_t r = sort_stream_join(ctx, sort_stream);
+    if (r) return r;
     if (wait_acc) HIPCHK(hipStreamWaitEvent(st, wait_acc, 0));
     if (ring) HIPCHK(hipEventRecord(ring[0], st));
     ctx->kname[0] = "c25519::k_small_cols (tables of multiples by repeated addition, one lane per (window, term))";
-    int32_t r = msm_small_enqueue(ctx, d_scalars, d_points, src_fmt, n, g, d_slot, st);
-    if (r) return r;
+    if ((r = msm_small_enqueue(ctx, call, d_scalars, d_points, src_fmt, n, g, d_slot, st))) return r;
     HIPCHK(hipEventRecord(ctx->ev_acc, st));
     if (ring) { HIPCHK(hipEventRecord(ring[1], st)); HIPCHK(hipEventRecord(ring[2], st)); }
     return C25519_OK;
 }
-int32_t msm_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, const msm_geom &g, uint32_t *d_slot, hipEvent_t *ring,
+int32_t msm_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, const msm_geom &g, uint32_t *d_slot, hipEvent_t *ring,
                     hipStream_t sort_stream, hipEvent_t wait_acc, const mid_run *run) {
-    if (n <= msm_small_max() && g.half <= 64) return msm_small_pass(ctx, d_scalars, d_pts, 1, n, g, d_slot, ring, sort_stream, wait_acc);   // (g.half: the layout may belong to larger sibling passes)
-    if (ctx->solo && !wait_acc && msm_mid_serves(n, g, true)) {          // (r6) a single pass of 12 288 .. 2^18 terms over prepared records: the mid path (mid.hip), on the main stream
-        hipStream_t st = ctx->stream;
-        if (!run && sort_stream && sort_stream != st) {              // (what the caller put on the second stream -- verify_batch: the batch scalars -- comes first)
-            HIPCHK(hipEventRecord(ctx->ev_sort, sort_stream));
-            HIPCHK(hipStreamWaitEvent(st, ctx->ev_sort, 0));
-        }
+    int32_t r;
+    if (n <= msm_small_max() && g.half <= 64) return msm_small_pass(ctx, call, d_scalars, d_pts, 1, n, g, d_slot, ring, sort_stream, wait_acc);   // (g.half: the layout may belong to larger sibling passes)
+    if (call.solo && !wait_acc && msm_mid_serves(n, g, true)) {          // (r6) a single pass of 12 288 .. 2^18 terms over prepared records: the mid path (mid.hip), on the main stream
+        if (!run && (r = sort_stream_join(ctx, sort_stream))) return r;      // (a pass with a stream override runs ON the stream of its scalars)
         // (no per-kernel events here either -- each is a ~5 us gap between two kernels of a chain that is all critical path: the ring entry of the caller (a verify_batch pass)
         //  is marked so that the accumulation / reduction phases of this call answer -1 instead of reading events of an older one; its own phases stay)
         if (ring) {
             const int idx = (int)((hipEvent_t(*)[c25519_ctx::RING_EV])ring - ctx->ring);
             if (idx >= 0 && idx < c25519_ctx::RING) ctx->ring_kind[idx] = (uint8_t)(ctx->ring_kind[idx] == 2 ? 3 : 4);      // 3: verify pass without MSM events, 4: MSM pass without them
         }
-        return msm_mid_enqueue(ctx, d_scalars, d_pts, 1, n, g, d_slot, 0, n, nullptr, run);
+        return msm_mid_enqueue(ctx, call, d_scalars, d_pts, 1, n, g, d_slot, 0, n, nullptr, run);
     }
     msm_plan pl;
-    int32_t r = msm_enqueue_sort(ctx, d_scalars, n, g, d_slot, sort_stream, pl);
-    if (r) return r;
-    return msm_enqueue_acc(ctx, pl, d_pts, d_slot, ring, wait_acc);
+    if ((r = msm_enqueue_sort(ctx, d_scalars, n, g, d_slot, sort_stream, pl))) return r;
+    return msm_enqueue_acc(ctx, call, pl, d_pts, d_slot, ring, wait_acc);
 }
 
 // total = sum_k 2^pos_k col_k by Horner (pippenger.rs:159), host arithmetic over <= 56 points
@@ -588,7 +586,7 @@ ge_p3 msm_horner(const uint32_t *cols, const msm_geom &g) {
 // hipMemcpyAsync of the slots into page-locked memory + hipStreamSynchronize (rounds 1-4, the default).  The round-4 verdict suspected 40 - 60 us of
 // copy-engine launch, interrupt and wake-up in there; round 5 built the alternative -- the last kernel WRITES the slots into the context's coherent,
 // device-mapped host buffer and releases a sequence word the host polls (k_publish; a long call first blocks on an event recorded at the end of its
-// last accumulation, ctx->coarse_wait, so that it does not burn a core for milliseconds) -- and measured it: 111.8 against 114.8 us for a 1-term MSM, level at every other size (profiles/r05_small_call_phases.txt,
+// last accumulation, msm_call::block_on, so that it does not burn a core for milliseconds) -- and measured it: 111.8 against 114.8 us for a 1-term MSM, level at every other size (profiles/r05_small_call_phases.txt,
 // r05_ab_publish.txt).  The end of a call costs ~3 us; what a small call spends is the host's launch work (~25 us), ~65 us of kernels and launch gaps on the
 // GPU and the host fold (~28 us).  The k_publish arm for LARGE calls stays behind the PUBLISH knob of the tuning build; the SMALL path's own publication
 // (small.hip small_direct, the release default since round 5) ends in wait_published below.
@@ -600,6 +598,22 @@ __global__ void __launch_bounds__(1024) k_publish(const u32 *__restrict__ src, u
     if (threadIdx.x == 0) __hip_atomic_store(host_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 }  // namespace c25519
+// ---- arming a publication: the one place that knows where the host's record slot and sequence word are ----
+static inline uint32_t *publish_rec(uint32_t *msm) { return msm + (size_t)C25519_MAX_SLOTS * C25519_SLOT_U32; }             // slot C25519_MAX_SLOTS of h_msm / hd_msm: the context's own record
+static inline uint32_t *publish_word(uint32_t *msm) { return msm + (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32; }     // the word behind the slots (ctx_make_streams)
+uint32_t publish_next_seq(c25519_ctx *ctx) {
+    uint32_t seq = ++ctx->publish_seq;
+    if (seq == 0) seq = ++ctx->publish_seq;                 // (0 means "does not publish")
+    return seq;
+}
+publish_target publish_arm(c25519_ctx *ctx, uint32_t seq) {
+    // fault injection (TUNING build only; the release library compiles this to nothing): every FAULT_LOSE_PUBLICATION-th directly published call releases a
+    // WRONG sequence number, so that tests exercise the host's recovery (wait_published phase 3, msm_call_run)
+    static const int lose_every = C25519_KNOB("FAULT_LOSE_PUBLICATION", 0);
+    const uint64_t nth = ++ctx->counters[C25519_CTR_PUBLISH_DIRECT];
+    if (lose_every > 0 && nth % (uint64_t)lose_every == 0) seq ^= 0x40000000u;
+    return {publish_rec(ctx->hd_msm), publish_word(ctx->hd_msm), seq};
+}
 static inline void cpu_relax() {
 #if defined(__x86_64__)
     __builtin_ia32_pause();
@@ -611,10 +625,10 @@ static inline void cpu_relax() {
 //      long as the STREAM takes; a GPU fault surfaces here as the stream's own error (round 5 returned hipErrorLaunchTimeOut after 60 s of polling whatever
 //      the stream was doing: ADVICE r5)
 //   3  the stream has drained without error and the word is still not there: a LOST publication.  Nothing of the kind has been observed (profiles/r06_soak_small.txt);
-//      the state is recorded in ctx->err (sequence word, expected number, the device's block counter), counted (c25519_ctx_counter), and the caller re-runs
+//      the state is recorded in ctx->err (sequence word, expected number, the device's block counter), counted (c25519_ctx_counter), and msm_call_run re-runs
 //      the call once through the slot + copy path of rounds 1-4, which needs no publication (C25519_LOST_PUBLICATION is internal: no entry point returns it).
 static int32_t wait_published(c25519_ctx *ctx, uint32_t seq) {
-    volatile uint32_t *vf = (uint32_t *)ctx->h_msm + (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32;
+    volatile uint32_t *vf = publish_word((uint32_t *)ctx->h_msm);
     static const double spin_us = (double)C25519_KNOB("PUBLISH_SPIN_US", 2000);
     const double t0 = wall_us();
     bool seen = false;
@@ -646,43 +660,49 @@ static int32_t wait_published(c25519_ctx *ctx, uint32_t seq) {
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     return C25519_OK;
 }
-static int32_t publish_and_wait(c25519_ctx *ctx, const uint32_t *d_src, uint32_t *h_dst, size_t words) {
-    uint32_t *flag = (uint32_t *)ctx->h_msm + (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32;      // the word behind the slots (ctx_make_streams)
-    uint32_t seq = ++ctx->publish_seq;
-    if (seq == 0) seq = ++ctx->publish_seq;
+static int32_t publish_and_wait(c25519_ctx *ctx, msm_call &call, const uint32_t *d_src, uint32_t *h_dst, size_t words) {
     ctx->host_us[2] = wall_us();                                          // everything is enqueued
     // Measured and NOT adopted (profiles/r05_small_call_phases.txt, r05_ab_publish.txt): 111.8 against 114.8 us for a 1-term MSM, level everywhere else -- the
     // copy engine + hipStreamSynchronize of rounds 1-4 cost ~3 us, not the 40 - 60 the verdict suspected; the default stays the simple path (knob 0).
     static const int publish = C25519_KNOB("PUBLISH", 0);
     if (!publish) {
-        ctx->coarse_wait = nullptr;
         HIPCHK(hipMemcpyAsync(h_dst, d_src, words * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         ctx->host_us[3] = wall_us();
         return C25519_OK;
     }
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(1024), 0, ctx->stream, d_src, h_dst, (uint32_t)words, flag, seq);
+    const uint32_t seq = publish_next_seq(ctx);               // (taken only here: the copy path above needs no number)
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(1024), 0, ctx->stream, d_src, h_dst, (uint32_t)words, publish_word((uint32_t *)ctx->h_msm), seq);
     HIPCHK(hipGetLastError());
-    if (ctx->coarse_wait) { (void)hipEventSynchronize(ctx->coarse_wait); ctx->coarse_wait = nullptr; }      // (blocking: the long part of a long call)
+    if (call.block_on) (void)hipEventSynchronize(call.block_on);      // (blocking: the long part of a long call)
     { const int32_t rw = wait_published(ctx, seq); if (rw) return rw; }
     ctx->host_us[3] = wall_us();                                          // the results are on the host
     return C25519_OK;
 }
 // slots [0, count) -> the host
-int32_t slots_collect(c25519_ctx *ctx, int count) {
-    return publish_and_wait(ctx, ctx->d_slots, (uint32_t *)ctx->h_msm, (size_t)count * C25519_SLOT_U32);
+int32_t slots_collect(c25519_ctx *ctx, msm_call &call, int count) {
+    return publish_and_wait(ctx, call, ctx->d_slots, (uint32_t *)ctx->h_msm, (size_t)count * C25519_SLOT_U32);
 }
 // the context's own record (slot C25519_MAX_SLOTS of d_slots / h_msm): where a call that answers on the host sums its passes
-int32_t rec_collect(c25519_ctx *ctx) {
-    if (ctx->direct_seq) {                                     // the small path publishes its record itself (small.hip): poll the sequence word
-        const uint32_t seq = ctx->direct_seq;
-        ctx->direct_seq = 0;
+int32_t rec_collect(c25519_ctx *ctx, msm_call &call) {
+    if (call.seq) {                                            // the small / mid path publishes its record itself (small.hip, reduce.hip): poll the sequence word
         ctx->host_us[2] = wall_us();
-        const int32_t r = wait_published(ctx, seq);
+        const int32_t r = wait_published(ctx, call.seq);
         ctx->host_us[3] = wall_us();
         return r;
     }
-    return publish_and_wait(ctx, drec(ctx), (uint32_t *)ctx->h_msm + (size_t)C25519_MAX_SLOTS * C25519_SLOT_U32, C25519_SLOT_U32);
+    return publish_and_wait(ctx, call, drec(ctx), publish_rec((uint32_t *)ctx->h_msm), C25519_SLOT_U32);
+}
+int32_t msm_call_run(c25519_ctx *ctx, const msm_call_enqueue &enqueue, int slots) {
+    for (int attempt = 0;; attempt++) {
+        msm_call call;
+        int32_t r = enqueue(attempt == 0, call);
+        if (r) return r;
+        r = (slots && !call.seq) ? slots_collect(ctx, call, slots) : rec_collect(ctx, call);
+        if (r == C25519_LOST_PUBLICATION && attempt == 0) continue;      // (r6) never observed; tests inject it (FAULT_LOSE_PUBLICATION)
+        if (!r && attempt) ctx->err.clear();                    // (the note of the lost publication: the call has its result)
+        return r;
+    }
 }
 void slot_init(uint32_t *d_slot, uint64_t terms, const uint32_t *d_pre, hipStream_t st, int c) {
     hipLaunchKernelGGL(k_slot_init, dim3(1), dim3(256), 0, st, d_slot, (uint32_t)terms, (uint32_t)(terms >> 32), terms ? 1u : 0u, (uint32_t)c, d_pre);
@@ -758,10 +778,11 @@ int32_t msm_core(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, const ui
         msm_layout(m, g);
         HIPCHK(hipMemsetAsync(dslot(ctx, 0), 0, C25519_SLOT_U32 * 4, ctx->stream));
         if (m) {
-            ctx->solo = true;
-            int32_t r = msm_enqueue(ctx, d_scalars + lo * 32, m, d_pts + lo * (PTS_BYTES / 4), g, dslot(ctx, 0), nullptr, nullptr);
+            msm_call call;
+            call.solo = true;
+            int32_t r = msm_enqueue(ctx, call, d_scalars + lo * 32, m, d_pts + lo * (PTS_BYTES / 4), g, dslot(ctx, 0), nullptr, nullptr);
             if (r) return r;
-            if ((r = slots_collect(ctx, 1))) return r;
+            if ((r = slots_collect(ctx, call, 1))) return r;
             if (slot_flags((uint32_t *)hslot(ctx, 0))[0]) return bad_arg(ctx, "msm: a scalar has bit 255 set (Scalar invariant #1 violated)");
             R = ge_add(R, msm_horner(hslot(ctx, 0), g));
         }
@@ -806,11 +827,12 @@ int32_t msm_merged_core(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, c
     msm_slice_params(g);
     HIPCHK(hipMemsetAsync(dslot(ctx, 0), 0, C25519_SLOT_U32 * 4, ctx->stream));
     msm_plan pl;
-    ctx->solo = true;
+    msm_call call;
+    call.solo = true;
     int32_t r = msm_enqueue_sort(ctx, d_scalars, n, g, dslot(ctx, 0), nullptr, pl, &m);
     if (r) return r;
-    if ((r = msm_enqueue_acc(ctx, pl, d_table, dslot(ctx, 0), nullptr, nullptr))) return r;
-    if ((r = slots_collect(ctx, 1))) return r;
+    if ((r = msm_enqueue_acc(ctx, call, pl, d_table, dslot(ctx, 0), nullptr, nullptr))) return r;
+    if ((r = slots_collect(ctx, call, 1))) return r;
     if (slot_flags((uint32_t *)hslot(ctx, 0))[0]) return bad_arg(ctx, "precomp_msm: internal error (top digit out of range)");
     R = host_p40(hslot(ctx, 0));                          // one window at position 0: the column sum IS the result
     return C25519_OK;
@@ -921,7 +943,7 @@ hipEvent_t *pass_ring(c25519_ctx *owner, c25519_ctx *c, uint8_t kind) {
 // (A third arm -- the launching pass normalising only its own points, the rest on a third stream behind the first two sorts -- was measured in rounds 5 and 6 and
 //  removed: 13.68 against 13.35 - 13.53 ms, with and without streaming accesses; profiles/r05_ab_prep_split.txt, r06_ab_mall.txt.)
 struct pts_ahead { uint32_t *pts; uint64_t n, offset; hipEvent_t done; bool launch; };
-static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const msm_geom &g, uint64_t terms, uint32_t *d_slot,
+static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const msm_geom &g, uint64_t terms, uint32_t *d_slot,
                                 hipEvent_t wait_acc, const pts_ahead *ahead = nullptr, hipEvent_t wait_in = nullptr,
                                 bool cont = false, bool reduce = true, uint64_t n_carve = 0, uint32_t *d_bad_sticky = nullptr) {
     int32_t r;
@@ -945,13 +967,13 @@ static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_
     const bool early = cont && !wait_in && terms > msm_small_max();
     const hipEvent_t lists_free = early ? ctx->ev_fork : nullptr;
     if (!early) HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-    if (!cont && !ctx->direct_seq) slot_init(d_slot, terms, nullptr, ctx->stream, g.c);            // (a continuing pass adds its counters to the slot of its stream set; a directly published small pass writes its whole record itself)
+    if (!cont) slot_init(d_slot, terms, nullptr, ctx->stream, g.c);            // (a continuing pass adds its counters to the slot of its stream set)
     if (terms <= msm_small_max() && g.half <= 64 && g.nwin <= 64 && !cont && reduce && !ahead) {      // (g: a forced width may not be the small path's -- then the bucket pipeline serves)
         // the small path (small.hip): raw points as they are (projective: no normalisation, no inversion); compressed ones through the
         // decompression into records first
-        if (in_fmt == C25519_FMT_RAW160) return msm_small_pass(ctx, d_scalars, d_points, 0, n, g, d_slot, ring, nullptr, wait_acc);
+        if (in_fmt == C25519_FMT_RAW160) return msm_small_pass(ctx, call, d_scalars, d_points, 0, n, g, d_slot, ring, nullptr, wait_acc);
         if ((r = prep_points(ctx, d_points, n, in_fmt, d_pts, 0, slot_flags(d_slot) + 1))) return r;
-        return msm_small_pass(ctx, d_scalars, d_pts, 1, n, g, d_slot, ring, nullptr, wait_acc);
+        return msm_small_pass(ctx, call, d_scalars, d_pts, 1, n, g, d_slot, ring, nullptr, wait_acc);
     }
     msm_plan pl;
     pl.bad_sticky = d_bad_sticky;
@@ -968,7 +990,7 @@ static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_
     // a continuing pass adds onto the bucket sums its predecessor on this stream set left: they must be where it left them
     if (cont && pl.buckets != ctx->cont_buckets) return bad_arg(ctx, "msm: internal error (the workspace of a continuing pass moved its buckets)");
     ctx->cont_buckets = pl.buckets;
-    if ((r = msm_enqueue_acc(ctx, pl, d_pts, d_slot, ring, wait_acc, cont, reduce, d_bad_sticky))) return r;
+    if ((r = msm_enqueue_acc(ctx, call, pl, d_pts, d_slot, ring, wait_acc, cont, reduce, d_bad_sticky))) return r;
     return C25519_OK;
 }
 // The whole MSM, enqueued: every pass on its stream set, the passes' column sums added on the device, the RECORD (column
@@ -977,8 +999,9 @@ static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_
 // scalars and points on the copy stream and returns the event the pass has to wait for -- so pass i computes while the inputs
 // of pass i+1 travel.  pass_terms (0 = default): terms per pass, smaller for host-pointer calls so that the link and the
 // kernels overlap at a finer grain.
+// allow_direct: the caller reads the record on the host right away and this is not the re-run of a lost publication; call: filled here, for rec_collect
 typedef std::function<int32_t(uint64_t lo, uint64_t m, hipEvent_t *ready)> msm_fetch;
-static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, uint32_t *d_record,
+static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, uint32_t *d_record, bool allow_direct, msm_call &call,
                                   const msm_fetch *fetch = nullptr, uint64_t pass_terms = 0) {
     HIPCHK(hipSetDevice(ctx->device));
     if (in_fmt < 0 || in_fmt > 2) return bad_arg(ctx, "msm: bad in_fmt");
@@ -997,13 +1020,12 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
     msm_geom g;
     pass_set ps;
     int32_t r;
+    call.solo = passes == 1;
     uint32_t *sticky = (uint32_t *)ctx->d_flag + 40;      // "a scalar has bit 255 set", ORed over the passes of the call
-    // (r5) A small call on raw points whose caller reads the record on the host right away (ctx->want_direct, d_record = the context's own record): the small
+    // (r5) A small call on raw points whose caller reads the record on the host right away (allow_direct, d_record = the context's own record): the small
     // path publishes the record itself -- no sticky-word memset and no k_slot_init before it, no copy launch behind it (small.hip small_direct):
     // 112 -> ~65 us for a 1-term call (profiles/r05_small_call_phases.txt).  A/B knob SMALL_DIRECT = 0: rounds 4's five launches.
     static const int small_direct_knob = C25519_KNOB("SMALL_DIRECT", 1);
-    ctx->direct_seq = 0;
-    ctx->direct_extra = nullptr;
     // (r6) the mid path (mid.hip: 12 288 .. 2^18 terms in four launches on this stream) publishes its record the same way
     bool mid = false;
     // (a host-pointer call of ONE pass has nothing to overlap its upload with: the inputs go up in one piece and the pass waits for them)
@@ -1012,54 +1034,47 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
     // 0.269 -> 0.236 ms, 6143 0.287 -> 0.244; 3072: 0.243 against 0.235, left alone)
     const bool enc_mid = in_fmt != C25519_FMT_RAW160 && n > verify_small_max() && n <= msm_small_max();
     if (passes == 1 && (n > msm_small_max() || enc_mid)) { msm_layout(n, g, 0, enc_mid ? 12 : 0); mid = msm_mid_serves(n, g, in_fmt != C25519_FMT_RAW160); }
-    if (small_direct_knob && ctx->want_direct && !ctx->no_direct_once && d_record == drec(ctx) && in_fmt == C25519_FMT_RAW160 && ((!fetch && n <= msm_small_max()) || mid)) {
+    if (small_direct_knob && allow_direct && d_record == drec(ctx) && in_fmt == C25519_FMT_RAW160 && ((!fetch && n <= msm_small_max()) || mid)) {
         msm_geom gs;
         msm_layout(n, gs);
-        if (mid || (gs.half <= 64 && gs.nwin <= 64)) { ctx->direct_seq = ++ctx->publish_seq; if (!ctx->direct_seq) ctx->direct_seq = ++ctx->publish_seq; }
+        if (mid || (gs.half <= 64 && gs.nwin <= 64)) call.seq = publish_next_seq(ctx);
     }
-    ctx->want_direct = false;
-    ctx->no_direct_once = false;
-    if (ctx->direct_seq && !mid) {
+    if (call.seq && !mid) {
         // (r6) the directly published small call, lean: its two kernels and the bracket of the call -- no phase ring, no fork to the second stream, no pass bookkeeping
         // (eight event records and a cross-stream wait that a 75 us call spent ~8 us of host time on; c25519_last_call_phase_ms answers -1 for such a call)
         msm_geom gs;
         msm_layout(n, gs);
         ctx->last_passes.clear();
-        ctx->solo = true;
-        ctx->coarse_wait = nullptr;
         ctx->kname[0] = "c25519::k_small_cols (tables of multiples by repeated addition, one lane per (window, term))";
-        if ((r = msm_small_enqueue(ctx, d_scalars, d_points, 0, n, gs, d_record, ctx->stream))) { ctx->direct_seq = 0; return r; }
+        if ((r = msm_small_enqueue(ctx, call, d_scalars, d_points, 0, n, gs, d_record, ctx->stream))) return r;
         HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
         return C25519_OK;
     }
     if (mid) {
         ctx->last_passes.clear();
-        ctx->solo = true;
-        ctx->coarse_wait = nullptr;
         // (no phase ring for the MSM's own mid-size calls: an event record between two kernels is a ~5 us gap on the GPU -- the lean small path got 30 us of GPU span
         //  back from eight of them; c25519_last_call_phase_ms answers -1, c25519_last_kernel_ms still brackets the call)
         hipEvent_t *ring = nullptr;
         if (fetch) {
             hipEvent_t in_ev = nullptr;
-            if ((r = (*fetch)(0, n, &in_ev))) { ctx->direct_seq = 0; return r; }
+            if ((r = (*fetch)(0, n, &in_ev))) return r;
             HIPCHK(hipStreamWaitEvent(ctx->stream, in_ev, 0));
         }
-        if (in_fmt == C25519_FMT_RAW160) r = msm_mid_enqueue(ctx, d_scalars, d_points, 0, n, g, d_record, 1, n, ring);
+        if (in_fmt == C25519_FMT_RAW160) r = msm_mid_enqueue(ctx, call, d_scalars, d_points, 0, n, g, d_record, 1, n, ring);
         else {
-            // encodings: the slot first (the decompression counts what does not decode into it), then the records, then the pass over them
-            ctx->direct_seq = 0;
+            // encodings (never published directly: call.seq is 0): the slot first (the decompression counts what does not decode into it), then the records, then the pass over them
             slot_init(d_record, n, nullptr, ctx->stream, g.c);
             if ((r = ctx_reserve(ctx, ctx->tmp_e, n * PTS_BYTES + 256))) return r;
             if ((r = prep_points(ctx, d_points, n, in_fmt, (uint32_t *)ctx->tmp_e.p, 0, slot_flags(d_record) + 1))) return r;
-            r = msm_mid_enqueue(ctx, d_scalars, ctx->tmp_e.p, 1, n, g, d_record, 0, n, ring);
+            r = msm_mid_enqueue(ctx, call, d_scalars, ctx->tmp_e.p, 1, n, g, d_record, 0, n, ring);
         }
-        if (r) { ctx->direct_seq = 0; return r; }
+        if (r) return r;
         HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
         return C25519_OK;
     }
     // (r5: letting the sort start on the second stream without the cross-stream wait when the main stream is idle measured level at 2^14 .. 2^20 terms --
     //  the ~20 us before the first kernels is launch latency, not the event: profiles/r05_ab_midrange_streams.txt; not kept)
-    if (!ctx->direct_seq) HIPCHK(hipMemsetAsync(sticky, 0, 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(sticky, 0, 4, ctx->stream));
     if ((r = passes_begin(ctx, passes, ps))) return r;
     // One layout for every pass: their column sums add up window by window.  It is derived from the terms of a pass -- or, when stream sets
     // get more than one pass each, from at least 2^21: their passes continue each other's bucket sums, ONE reduction serves all of them, and
@@ -1067,7 +1082,6 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
     // carries the number the layout was derived from (records_fold re-derives it from there).
     const uint64_t layout_terms = (passes > (uint64_t)ps.lanes && per >= (1ull << 20)) ? std::max<uint64_t>(per, 1ull << 21) : per;
     msm_layout(layout_terms, g);
-    ctx->solo = passes == 1;               // (overwritten by every call: an early error return leaves nothing behind that a later call would read)
     hipEvent_t prev_acc = nullptr;                         // the accumulation of the previous pass (on the other stream set)
     hipEvent_t prev_acc_last = nullptr;
     // raw points, several passes on two stream sets: pass 1 (the first one on the peer) prepares the records of ALL later
@@ -1090,7 +1104,7 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
         uint32_t *slot = passes == 1 ? d_record : dslot(ctx, l);         // a single pass writes the record itself
         hipEvent_t in_ev = nullptr;
         if (fetch && (r = (*fetch)(lo, m, &in_ev))) return r;
-        if ((r = msm_pass_enqueue(ctx, c, d_scalars + lo * 32, d_points + lo * psz, m, in_fmt, g, layout_terms, slot, prev_acc, (ahead && p >= 1) ? &ah : nullptr, in_ev,
+        if ((r = msm_pass_enqueue(ctx, c, call, d_scalars + lo * 32, d_points + lo * psz, m, in_fmt, g, layout_terms, slot, prev_acc, (ahead && p >= 1) ? &ah : nullptr, in_ev,
                                   !first, last, per, sticky))) {
             if (ctx->err.empty()) ctx->err = c->err;
             return r;
@@ -1099,7 +1113,7 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
         prev_acc_last = c->ev_acc;
     }
     // a long call: the host blocks on the end of the LAST accumulation before it polls for the published results (publish_and_wait)
-    ctx->coarse_wait = (n >= (1ull << 17) && prev_acc_last) ? prev_acc_last : nullptr;
+    call.block_on = (n >= (1ull << 17) && prev_acc_last) ? prev_acc_last : nullptr;
     if ((r = passes_join(ctx, ps))) return r;
     if (passes > 1) hipLaunchKernelGGL(k_record_sum, dim3(1), dim3(128), 0, ctx->stream, d_record, ctx->d_slots, (int)std::min<uint64_t>((uint64_t)L, passes), g.nwin, 1);
     HIPCHK(hipGetLastError());
@@ -1113,16 +1127,7 @@ static int32_t msm_record_status(c25519_ctx *ctx, const uint32_t flags[8]) {
 }
 static int32_t msm_partial_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, ge_p3 &R) {
     ctx->host_us[0] = ctx->host_us[1] = wall_us();
-    ctx->want_direct = true;
-    int32_t r = msm_record_enqueue(ctx, d_scalars, d_points, n, in_fmt, drec(ctx));
-    if (r) { ctx->direct_seq = 0; return r; }
-    r = rec_collect(ctx);
-    if (r == C25519_LOST_PUBLICATION) {                     // (r6) never observed; see wait_published: once more through the slot + copy path
-        ctx->no_direct_once = true;
-        if ((r = msm_record_enqueue(ctx, d_scalars, d_points, n, in_fmt, drec(ctx)))) return r;
-        r = rec_collect(ctx);
-        if (!r) ctx->err.clear();
-    }
+    int32_t r = msm_call_run(ctx, [&](bool allow_direct, msm_call &call) { return msm_record_enqueue(ctx, d_scalars, d_points, n, in_fmt, drec(ctx), allow_direct, call); });
     if (r) return r;
     uint32_t flags[8];
     if ((r = records_fold((const uint8_t *)hslot(ctx, C25519_MAX_SLOTS), 1, R, flags, &ctx->err))) return r;
@@ -1132,7 +1137,8 @@ static int32_t msm_partial_impl(c25519_ctx *ctx, const uint8_t *d_scalars, const
 // This rank's (context's) share of a sharded MSM as a RECORD in device memory: enqueue only.  The records
 // of all ranks are exchanged (one all_gather over RCCL) and folded once by c25519_fold_partial_records.
 EXPORT int32_t c25519_msm_partial_record_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, uint8_t *d_record) {
-    return msm_record_enqueue(ctx, d_scalars, d_points, n, in_fmt, (uint32_t *)d_record);
+    msm_call call;                                         // (enqueue only: nobody collects)
+    return msm_record_enqueue(ctx, d_scalars, d_points, n, in_fmt, (uint32_t *)d_record, false, call);
 }
 EXPORT int32_t c25519_fold_partial_records(c25519_ctx *ctx, const uint8_t *records, uint64_t count, int out_fmt, uint8_t *out) {
     if (out_fmt < 0 || out_fmt > 2) { if (ctx) ctx->err = "fold: bad out_fmt"; return -(int32_t)hipErrorInvalidValue; }
@@ -1199,16 +1205,11 @@ EXPORT int32_t c25519_msm_vartime(c25519_ctx *ctx, const uint8_t *scalars, const
         ctx->host_us[1] = wall_us();
         ge_p3 R;
         uint32_t flags[8];
-        ctx->want_direct = true;
-        r = msm_record_enqueue(ctx, d[0], d[1], n, in_fmt, drec(ctx));
-        if (!r) r = rec_collect(ctx);
-        else { ctx->direct_seq = 0; (void)hipStreamSynchronize(ctx->stream); }          // (the upload may still be reading the staging buffer)
-        if (r == C25519_LOST_PUBLICATION) {                 // (r6) never observed; see wait_published: once more through the slot + copy path (the staged inputs are still there)
-            ctx->no_direct_once = true;
-            r = msm_record_enqueue(ctx, d[0], d[1], n, in_fmt, drec(ctx));
-            if (!r) r = rec_collect(ctx);
-            if (!r) ctx->err.clear();
-        }
+        r = msm_call_run(ctx, [&](bool allow_direct, msm_call &call) {      // (a re-run finds the staged inputs still there)
+            const int32_t q = msm_record_enqueue(ctx, d[0], d[1], n, in_fmt, drec(ctx), allow_direct, call);
+            if (q) (void)hipStreamSynchronize(ctx->stream);          // (the upload may still be reading the staging buffer)
+            return q;
+        });
         ffi_small_end(ctx, n * (32 + psz), 0);
         if (r) return r;
         if ((r = records_fold((const uint8_t *)hslot(ctx, C25519_MAX_SLOTS), 1, R, flags, &ctx->err))) return r;
@@ -1240,15 +1241,10 @@ EXPORT int32_t c25519_msm_vartime(c25519_ctx *ctx, const uint8_t *scalars, const
     ge_p3 R;
     uint32_t flags[8];
     const uint64_t pass_terms = n >= (1ull << 20) ? (in_fmt == C25519_FMT_RAW160 ? (1ull << 19) : (1ull << 20)) : 0;
-    ctx->want_direct = true;                               // (the mid path publishes its record itself; the bucket pipeline ignores the wish)
-    r = msm_record_enqueue(ctx, d_s, d_p, n, in_fmt, drec(ctx), &fetch, pass_terms);
-    if (!r) r = rec_collect(ctx);
-    if (r == C25519_LOST_PUBLICATION) {                     // (never observed; see wait_published: once more through the slot + copy path -- the inputs are on the device)
-        ctx->no_direct_once = true;
-        r = msm_record_enqueue(ctx, d_s, d_p, n, in_fmt, drec(ctx), nullptr, 0);
-        if (!r) r = rec_collect(ctx);
-        if (!r) ctx->err.clear();
-    }
+    // (the mid path publishes its record itself; the bucket pipeline ignores the wish.  A re-run finds the inputs on the device: no fetch)
+    r = msm_call_run(ctx, [&](bool allow_direct, msm_call &call) {
+        return msm_record_enqueue(ctx, d_s, d_p, n, in_fmt, drec(ctx), allow_direct, call, allow_direct ? &fetch : nullptr, allow_direct ? pass_terms : 0);
+    });
     guard.dismiss();
     const int32_t r2 = ffi_end(ctx, up, 0);
     if (r || (r = r2)) return r;

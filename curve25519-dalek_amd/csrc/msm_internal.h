@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <functional>
 #include "ge26.h"
 #include "ctx.h"
 
@@ -68,6 +69,23 @@ static inline uint32_t *dslot(c25519_ctx *ctx, int i) { return ctx->d_slots + (s
 static inline const uint32_t *hslot(c25519_ctx *ctx, int i) { return (const uint32_t *)ctx->h_msm + (size_t)i * C25519_SLOT_U32; }
 // the context's own record (slot C25519_MAX_SLOTS of d_slots / h_msm): where a call that answers on the host sums its passes
 static inline uint32_t *drec(c25519_ctx *ctx) { return dslot(ctx, C25519_MAX_SLOTS); }
+// How ONE call answers: a local of the entry point, handed down through everything it enqueues and on to the collect functions -- never state of a context
+// (a pass dealt to the peer context reads the call's, and an error return leaves nothing behind for the next call)
+struct msm_call {
+    bool solo = false;                     // in: ONE pass on the call's own context -- its bucket reduction may run on the main stream (msm_enqueue_acc), the mid path may serve it (msm_enqueue)
+    uint32_t seq = 0;                      // in: != 0 -- the last kernel publishes the record itself under this sequence number (publish_next_seq); 0 -- the slot + copy path
+    const uint32_t *extra = nullptr;       // in, with seq: two device words to publish as the record's counters [2], [3] (verify.hip, small batches)
+    hipEvent_t block_on = nullptr;         // out, set by the enqueue functions of a long call: the host blocks on it before it polls for the results (publish_and_wait)
+};
+// arming a publication (msm.hip): the context's next non-zero sequence number; then, for the enqueue that publishes under it, the DEVICE's view of the host record
+// slot and of the sequence word and the number to release there (counts the call in C25519_CTR_PUBLISH_DIRECT; the tuning build's loss injection changes the number)
+uint32_t publish_next_seq(c25519_ctx *ctx);
+struct publish_target { uint32_t *rec, *word; uint32_t seq; };
+publish_target publish_arm(c25519_ctx *ctx, uint32_t seq);
+// enqueue(allow_direct = true, call), collect; a lost publication (msm.hip wait_published) runs both once more with allow_direct = false -- the slot + copy path.
+// slots: 0 collects the context's own record (rec_collect); n > 0 the slots [0, n), unless the call published its record itself (verify_batch, device z-mode)
+typedef std::function<int32_t(bool allow_direct, msm_call &call)> msm_call_enqueue;
+int32_t msm_call_run(c25519_ctx *ctx, const msm_call_enqueue &enqueue, int slots = 0);
 // An MSM pass is enqueued in two halves so that a caller can put other work between them (msm.hip):
 //   msm_enqueue_sort  the counting sort of the term indices by bucket, bucket order, long-bucket work list -- needs only the SCALARS
 //   msm_enqueue_acc   accumulation (+ the long-bucket path on the second stream) and bucket reduction -- needs the POINTS (affine Niels records)
@@ -85,19 +103,20 @@ struct msm_matrix_sort_args {
     uint16_t *D; uint32_t *counts, *P1, *cc, *bin_base, *flags, *totals, *ord_hist;
 };
 int32_t msm_matrix_sort_enqueue(c25519_ctx *ctx, const c25519::msm_geom &g, const c25519::msm_merged *md, msm_plan &pl, const msm_matrix_sort_args &a, hipStream_t st);
-int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_plan &pl, const uint32_t *d_pts, uint32_t *d_slot, hipEvent_t *ring, hipEvent_t wait_acc, bool cont = false, bool reduce = true,
-                        const uint32_t *d_bad_sticky = nullptr);
+int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_call &call, const msm_plan &pl, const uint32_t *d_pts, uint32_t *d_slot, hipEvent_t *ring, hipEvent_t wait_acc, bool cont = false,
+                        bool reduce = true, const uint32_t *d_bad_sticky = nullptr);
 struct mid_run;
 // sort + accumulate + reduce of one pass over prepared records; inputs of at most msm_small_max() terms take the small path (run: see msm_mid_enqueue; honoured by the mid path only)
-int32_t msm_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, const c25519::msm_geom &g, uint32_t *d_slot, hipEvent_t *ring,
+int32_t msm_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, const c25519::msm_geom &g, uint32_t *d_slot, hipEvent_t *ring,
                     hipStream_t sort_stream, hipEvent_t wait_acc = nullptr, const struct mid_run *run = nullptr);
 // the whole MSM of at most msm_small_max() terms in two launches, column sums of the layout g to d_slot (small.hip).  src_fmt: 0 = raw 160-byte points,
-// 1 = affine Niels records (128 bytes); flags: the slot's counters (bit 255 of a scalar is ORed into flags[0])
-int32_t msm_small_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const c25519::msm_geom &g, uint32_t *d_slot, hipStream_t st);
+// 1 = affine Niels records (128 bytes); flags: the slot's counters (bit 255 of a scalar is ORed into flags[0]).  call.seq != 0: the record is published instead
+int32_t msm_small_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const c25519::msm_geom &g, uint32_t *d_slot,
+                          hipStream_t st);
 c25519::ge_p3 host_p40(const uint32_t *t);
 c25519::ge_p3 msm_horner(const uint32_t *cols, const c25519::msm_geom &g);
-int32_t slots_collect(c25519_ctx *ctx, int count);
-int32_t rec_collect(c25519_ctx *ctx);
+int32_t slots_collect(c25519_ctx *ctx, msm_call &call, int count);
+int32_t rec_collect(c25519_ctx *ctx, msm_call &call);
 void slot_init(uint32_t *d_slot, uint64_t terms, const uint32_t *d_pre, hipStream_t st, int c);
 int32_t records_fold(const uint8_t *records, uint64_t count, c25519::ge_p3 &R, uint32_t flags[8], std::string *err);
 struct pass_set { c25519_ctx *c[4]; int lanes; };
@@ -123,8 +142,8 @@ bool msm_mid_serves(uint64_t n, const c25519::msm_geom &g, bool prepared);      
 // records sign_first .. sign_first + sign_count - 1 whose sign_z16 entry (16 bytes each, bit 127) is set (verify.hip k_apply_sign: the sign of the device z-mode's z_i);
 // the context's main stream continues behind the pass
 struct mid_run { hipStream_t stream; hipEvent_t recs_ready; const uint8_t *sign_z16; uint64_t sign_first, sign_count; };
-int32_t msm_mid_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const void *points, int src_fmt, uint64_t n, const c25519::msm_geom &g, uint32_t *d_slot, int hdr, uint64_t terms, hipEvent_t *ring,
-                        const mid_run *run = nullptr);
+int32_t msm_mid_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const void *points, int src_fmt, uint64_t n, const c25519::msm_geom &g, uint32_t *d_slot, int hdr,
+                        uint64_t terms, hipEvent_t *ring, const mid_run *run = nullptr);
 void launch_apply_sign(uint32_t *pts, uint64_t dst0, const uint8_t *z16, uint64_t n, hipStream_t st);      // verify.hip
 void launch_prep_basepoint(uint32_t *pts, uint64_t dst, hipStream_t st);
 void launch_record_sum(uint32_t *rec, const uint32_t *slots, int cnt, int nwin, int first, hipStream_t st);

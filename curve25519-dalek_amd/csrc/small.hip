@@ -213,22 +213,18 @@ __global__ void __launch_bounds__(TH) k_small_reduce(const u32 *__restrict__ par
 
 }  // namespace c25519
 
-int32_t msm_small_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const msm_geom &g, uint32_t *d_slot, hipStream_t st) {
+int32_t msm_small_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const msm_geom &g, uint32_t *d_slot, hipStream_t st) {
     if (n == 0 || n > msm_small_max() || g.half > 64 || g.nwin > SMALL_SLOTS) return bad_arg(ctx, "msm: internal error (small path outside its range)");
     const int nblocks = (int)((n + SMALL_T - 1) / SMALL_T);
     const size_t lds = (size_t)SMALL_T * g.half * 160;
-    // direct publication (ctx->direct_seq, set by msm_record_enqueue): the record goes to the host's slot, not to d_slot
+    // direct publication (call.seq, set by msm_record_enqueue / verify.hip): the record goes to the host's slot, not to d_slot
     small_direct dx = {0, nullptr, nullptr, nullptr, 0, 0, 0, nullptr};
     uint32_t *out = d_slot;
-    if (ctx->direct_seq) {
-        out = ctx->hd_msm + (size_t)C25519_MAX_SLOTS * C25519_SLOT_U32;
-        dx.on = 1; dx.done_cnt = (uint32_t *)ctx->d_flag + 56; dx.host_flag = ctx->hd_msm + (size_t)(C25519_MAX_SLOTS + 1) * C25519_SLOT_U32;
-        dx.seq = ctx->direct_seq; dx.terms = (uint32_t)n; dx.c = (uint32_t)g.c; dx.extra = ctx->direct_extra;
-        // fault injection (TUNING build only; the release library compiles this to nothing): every FAULT_LOSE_PUBLICATION-th directly published call releases a
-        // WRONG sequence number, so that the host's recovery -- wait_published phase 3 and the re-run through the copy path -- is exercised by a test
-        static const int lose_every = C25519_KNOB("FAULT_LOSE_PUBLICATION", 0);
-        const uint64_t nth = ++ctx->counters[C25519_CTR_PUBLISH_DIRECT];
-        if (lose_every > 0 && nth % (uint64_t)lose_every == 0) dx.seq ^= 0x40000000u;
+    if (call.seq) {
+        const publish_target pt = publish_arm(ctx, call.seq);
+        out = pt.rec;
+        dx.on = 1; dx.done_cnt = (uint32_t *)ctx->d_flag + 56; dx.host_flag = pt.word;
+        dx.seq = pt.seq; dx.terms = (uint32_t)n; dx.c = (uint32_t)g.c; dx.extra = call.extra;
     }
     uint32_t *partial = out;                                        // a single block writes the column sums themselves
     if (nblocks > 1) {

@@ -424,7 +424,7 @@ struct verify_pre { hipEvent_t ready; const uint32_t *cnt; };
 __global__ void k_add_point_counters(u32 *__restrict__ d_cnt, const u32 *__restrict__ cnt) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { d_cnt[2] += cnt[0]; d_cnt[3] += cnt[1]; }
 }
-static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len,
+static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm_call &call, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len,
                                    const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points, uint64_t n, uint32_t z_mode,
                                    const uint8_t *d_hram_pre, const uint8_t *d_z_pre, const uint32_t *d_pre_flags, const msm_geom &g, uint64_t terms, uint32_t *d_slot, hipEvent_t wait_acc,
                                    const verify_stage *stage = nullptr, const verify_pre *pre = nullptr) {
@@ -470,7 +470,7 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uin
     // A batch whose MSM takes the mid path (mid.hip) runs that MSM on THIS stream, right behind its scalars: the digits and the sort need nothing else; the records
     // (main stream) are waited for once, in front of the accumulation, and the sign of z_i is applied to R_i there (msm_mid_enqueue, mid_run).  Before: k_bsum_finish ->
     // 30 us (event, k_apply_sign on the main stream, event) -> k_mid_front at 2^14 signatures, plus an event record between k_zderive and k_batch_scalars.
-    const bool on_chain = !stage && !d_hram_pre && !d_z_pre && ctx->solo && !wait_acc && !pre && verify_on_chain(n, g, false);
+    const bool on_chain = !stage && !d_hram_pre && !d_z_pre && call.solo && !wait_acc && !pre && verify_on_chain(n, g, false);
     if (chain_first) {
         if ((r = zchain_enqueue(ctx, sa, hred, d_sigs, n, t0, t1, z16))) return r;
         if (!on_chain) HIPCHK(hipEventRecord(ctx->ev_z, sa));
@@ -540,11 +540,11 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const uin
     if (on_chain) {
         HIPCHK(hipEventRecord(ctx->ev_pts, st));                       // the records of B, R_i and A_i
         const mid_run run = {sa, ctx->ev_pts, z16, 1, n};
-        return msm_enqueue(ctx, msc, m, d_pts, g, d_slot, ring, sa, wait_acc, &run);
+        return msm_enqueue(ctx, call, msc, m, d_pts, g, d_slot, ring, sa, wait_acc, &run);
     }
     if (stage && d_pk_points && (r = prep_A())) return r;   // the keys' points come last: only the accumulation needs them
     // the MSM's digit/sort phase continues on the second stream while (S) is still decompressing
-    return msm_enqueue(ctx, msc, m, d_pts, g, d_slot, ring, sa, wait_acc);
+    return msm_enqueue(ctx, call, msc, m, d_pts, g, d_slot, ring, sa, wait_acc);
 }
 // Batches beyond ~1.5 * 2^20 signatures are checked as several independent random linear combinations of about
 // 2^20 signatures each (same reason as MSM_PASS_MAX; in the device z-mode every pass derives its own z_i from its own
@@ -568,7 +568,7 @@ static int32_t verify_record_verdict(c25519_ctx *ctx, const ge_p3 &R, const uint
 // 64-byte trailer of counters -- [0] non-canonical s, [1] bad offsets -- as ed25519_batch_hram_dev leaves them; d_z16 = their
 // z_i), summed into ONE record at d_record: the reference's single equation (batch.rs:235-250) whatever the pass split.
 static int32_t verify_record_enqueue(c25519_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points, const uint8_t *d_hram, const uint8_t *d_z16,
-                                     uint64_t n, uint32_t *d_record, const verify_pre *pre = nullptr) {
+                                     uint64_t n, uint32_t *d_record, msm_call &call, const verify_pre *pre = nullptr) {
     HIPCHK(hipSetDevice(ctx->device));
     if (n >= (1ull << 40)) return bad_arg(ctx, "verify_batch: n too large");
     const uint32_t *d_pre = (const uint32_t *)(d_hram + n * 64);
@@ -579,7 +579,7 @@ static int32_t verify_record_enqueue(c25519_ctx *ctx, const uint8_t *d_sigs, con
     int32_t r;
     pass_set ps;
     if ((r = passes_begin(ctx, passes, ps))) return r;
-    ctx->solo = passes == 1;               // one pass on this context alone: its reduction runs on the main stream (msm.hip msm_enqueue_acc)
+    call.solo = passes == 1;               // one pass on this context alone: its reduction runs on the main stream (msm.hip msm_enqueue_acc)
     hipEvent_t prev_acc = nullptr;
     for (uint64_t p0 = 0; p0 < passes; p0 += C25519_MAX_SLOTS) {
         const int cnt = (int)std::min<uint64_t>(C25519_MAX_SLOTS, passes - p0);
@@ -591,7 +591,7 @@ static int32_t verify_record_enqueue(c25519_ctx *ctx, const uint8_t *d_sigs, con
             const uint64_t lo = (p0 + i) * per, m = std::min(per, n - lo);
             c25519_ctx *c = ps.c[(p0 + i) % ps.lanes];
             uint32_t *slot = passes == 1 ? d_record : dslot(ctx, i);
-            r = verify_pass_enqueue(ctx, c, nullptr, nullptr, 0, d_sigs + lo * 64, d_pks + lo * 32, d_pk_points ? d_pk_points + lo * 160 : nullptr, m, C25519_Z_TRANSCRIPT,
+            r = verify_pass_enqueue(ctx, c, call, nullptr, nullptr, 0, d_sigs + lo * 64, d_pks + lo * 32, d_pk_points ? d_pk_points + lo * 160 : nullptr, m, C25519_Z_TRANSCRIPT,
                                     d_hram + lo * 64, d_z16 + lo * 16, (p0 + i == 0) ? d_pre : nullptr, g, 2 * per + 1, slot, prev_acc, nullptr, passes == 1 ? pre : nullptr);
             if (r) { if (ctx->err.empty()) ctx->err = c->err; return r; }
             prev_acc = ps.lanes > 1 ? c->ev_acc : nullptr;
@@ -622,7 +622,8 @@ EXPORT int32_t ed25519_batch_transcript_zs(const uint8_t *hram, const uint8_t *s
 }
 EXPORT int32_t ed25519_verify_batch_record_dev(c25519_ctx *ctx, const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points, const uint8_t *d_hram, const uint8_t *d_z16,
                                                uint64_t n, uint8_t *d_record) {
-    return verify_record_enqueue(ctx, d_sigs, d_pks, d_pk_points, d_hram, d_z16, n, (uint32_t *)d_record);
+    msm_call call;                                         // (enqueue only: nobody collects)
+    return verify_record_enqueue(ctx, d_sigs, d_pks, d_pk_points, d_hram, d_z16, n, (uint32_t *)d_record, call);
 }
 EXPORT int32_t ed25519_fold_verify_records(c25519_ctx *ctx, const uint8_t *records, uint64_t count) {
     ge_p3 R;
@@ -644,6 +645,7 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     int32_t r;
     if (z_mode == C25519_Z_TRANSCRIPT) {
+        msm_call call;
         // the reference's sequential Merlin transcript (batch.rs:168-222) over the WHOLE batch, on one host core; then ONE
         // equation over the whole batch (the passes' column sums are added on the device), exactly batch.rs:235-250
         try {
@@ -673,10 +675,10 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
             HIPCHK(hipStreamSynchronize(ctx->stream));
             c25519_transcript_zs(hh, hs, n, hz);
             HIPCHK(hipMemcpyAsync(d_z_all, hz, n * 16, hipMemcpyHostToDevice, ctx->stream));
-            if ((r = verify_record_enqueue(ctx, d_sigs, d_pks, d_pk_points, d_hram_all, d_z_all, n, drec(ctx), pre_pts.ready ? &pre_pts : nullptr))) return r;
+            if ((r = verify_record_enqueue(ctx, d_sigs, d_pks, d_pk_points, d_hram_all, d_z_all, n, drec(ctx), call, pre_pts.ready ? &pre_pts : nullptr))) return r;
         } catch (const std::exception &e) { ctx->err = std::string("verify_batch: ") + e.what(); return -(int32_t)hipErrorOutOfMemory; }
-        if (n >= (1ull << 16)) ctx->coarse_wait = ctx->ev_acc;          // a long call blocks on its accumulation before it polls for the published record (msm.hip publish_and_wait)
-        if ((r = rec_collect(ctx))) return r;
+        if (n >= (1ull << 16)) call.block_on = ctx->ev_acc;          // a long call blocks on its accumulation before it polls for the published record (msm.hip publish_and_wait)
+        if ((r = rec_collect(ctx, call))) return r;
         HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
         ge_p3 R;
         uint32_t flags[8];
@@ -700,41 +702,38 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
     else if (verify_c == 0 && passes == 1 && msm_mid_serves_terms(vterms)) vc = vterms < 8192 ? 12 : vterms < 24576 ? 13 : vterms < 98304 ? 14 : 16;
     msm_layout(vterms, g, 16, vc);        // (the z_i are 128-bit: with 16-bit windows they end on a window boundary; a 17-bit layout leaves a 9-bit stub of 2^20 equal-ish digits)
     pass_set ps;
-    if ((r = passes_begin(ctx, passes, ps))) return r;
-    ctx->solo = passes == 1;
     // (r6) a single pass through the mid path, inputs on the device: the last reduction block publishes the record -- columns and the slot's counters -- into the
-    // context's page-locked host slot and the host polls the sequence word (msm.hip wait_published, with the small path's recovery: a lost publication re-runs the
-    // batch once through the slot + copy path) instead of a copy-engine launch and a blocking synchronisation behind the last kernel
+    // context's page-locked host slot and the host polls the sequence word (msm.hip wait_published; msm_call_run has the small path's recovery: a lost publication
+    // re-runs the pass once through the slot + copy path) instead of a copy-engine launch and a blocking synchronisation behind the last kernel
     static const int verify_direct_knob = C25519_KNOB("VERIFY_DIRECT", 1);
-    const bool direct = passes == 1 && !fetch && verify_direct_knob && !ctx->no_direct_once && ps.c[0] == ctx && verify_on_chain(n, g, false);
-    ctx->no_direct_once = false;
-    ctx->direct_seq = 0;
-    if (direct) { ctx->direct_seq = ++ctx->publish_seq; if (!ctx->direct_seq) ctx->direct_seq = ++ctx->publish_seq; }
+    const bool may_publish = passes == 1 && !fetch && verify_direct_knob && verify_on_chain(n, g, false);
+    // (only a call of ONE pass publishes, so a loss can only happen in the first -- the only -- group: the re-run below starts the pass list again.  ev0 and
+    //  host_us[0..1] are NOT taken again: after a recovery c25519_last_kernel_ms and the host clock span both attempts)
+    bool direct = false;                   // did the latest attempt publish its record (host slot C25519_MAX_SLOTS) instead of leaving it in slot 0
     bool seen[5] = {false, false, false, false, false}, bad_off = false, bad_scalar = false;
     hipEvent_t prev_acc = nullptr;
     for (uint64_t p0 = 0; p0 < passes; p0 += C25519_MAX_SLOTS) {
         const int cnt = (int)std::min<uint64_t>(C25519_MAX_SLOTS, passes - p0);
-        for (int i = 0; i < cnt; i++) {
-            const uint64_t lo = (p0 + i) * per, m = std::min(per, n - lo);
-            c25519_ctx *c = ps.c[(p0 + i) % ps.lanes];
-            const verify_stage stage = [&](int what, hipEvent_t *ready) -> int32_t { return (*fetch)(lo, m, what, ready); };
-            r = verify_pass_enqueue(ctx, c, d_msgs, d_msg_off + lo, msgs_len, d_sigs + lo * 64, d_pks + lo * 32, d_pk_points ? d_pk_points + lo * 160 : nullptr, m, z_mode,
-                                    nullptr, nullptr, nullptr, g, 2 * per + 1, dslot(ctx, i), prev_acc, fetch ? &stage : nullptr);
-            if (r) { ctx->direct_seq = 0; if (ctx->err.empty()) ctx->err = c->err; return r; }
-            prev_acc = ps.lanes > 1 ? c->ev_acc : nullptr;
-            if (n >= (1ull << 16) && !direct) ctx->coarse_wait = c->ev_acc;
-        }
-        if ((r = passes_join(ctx, ps))) { ctx->direct_seq = 0; return r; }
-        if (direct) {
-            r = rec_collect(ctx);                           // (polls for ctx->direct_seq and clears it)
-            if (r == C25519_LOST_PUBLICATION) {             // never observed (profiles/r06_soak_small.txt); tests/test_gpu_verify.py injects it
-                ctx->no_direct_once = true;
-                const int32_t r2 = verify_batch_impl(ctx, d_msgs, d_msg_off, msgs_len, d_sigs, d_pks, d_pk_points, n, z_mode, fetch);
-                if (r2 >= 0) ctx->err.clear();              // (the note of the lost publication: the call has its verdict)
-                return r2;
+        // the passes of this group, then their slots -- or the one published record -- on the host
+        r = msm_call_run(ctx, [&](bool allow_direct, msm_call &call) -> int32_t {
+            int32_t q;
+            if (p0 == 0 && (q = passes_begin(ctx, passes, ps))) return q;
+            call.solo = passes == 1;
+            direct = allow_direct && may_publish && ps.c[0] == ctx;
+            if (direct) call.seq = publish_next_seq(ctx);
+            for (int i = 0; i < cnt; i++) {
+                const uint64_t lo = (p0 + i) * per, m = std::min(per, n - lo);
+                c25519_ctx *c = ps.c[(p0 + i) % ps.lanes];
+                const verify_stage stage = [&](int what, hipEvent_t *ready) -> int32_t { return (*fetch)(lo, m, what, ready); };
+                q = verify_pass_enqueue(ctx, c, call, d_msgs, d_msg_off + lo, msgs_len, d_sigs + lo * 64, d_pks + lo * 32, d_pk_points ? d_pk_points + lo * 160 : nullptr, m, z_mode,
+                                        nullptr, nullptr, nullptr, g, 2 * per + 1, dslot(ctx, i), prev_acc, fetch ? &stage : nullptr);
+                if (q) { if (ctx->err.empty()) ctx->err = c->err; return q; }
+                prev_acc = ps.lanes > 1 ? c->ev_acc : nullptr;
+                if (n >= (1ull << 16) && !direct) call.block_on = c->ev_acc;
             }
-            if (r) return r;
-        } else if ((r = slots_collect(ctx, cnt))) return r;
+            return passes_join(ctx, ps);
+        }, cnt);
+        if (r) return r;
         for (int i = 0; i < cnt; i++) {
             const uint32_t *s = hslot(ctx, direct ? C25519_MAX_SLOTS : i), *f = s + MSM_MAX_WIN * 40;
             if (f[0]) bad_scalar = true;
@@ -870,23 +869,19 @@ static int32_t verify_batch_small_host(c25519_ctx *ctx, const uint8_t *msgs, con
     }
     { uint32_t o[8]; sc_to_words(sc_neg(sum), o); memcpy(msc, o, 32); }      // B: -sum z_i s_i   (batch.rs:240)
     // ---- the MSM of 2n + 1 terms over the records, published by its last kernel ----
-    ctx->direct_seq = ++ctx->publish_seq;
-    if (!ctx->direct_seq) ctx->direct_seq = ++ctx->publish_seq;
-    ctx->direct_extra = cnt;
-    r = msm_small_enqueue(ctx, dv + oC, d_pts, 1, m, g, drec(ctx), ctx->stream);
-    ctx->direct_extra = nullptr;
-    if (r) { ctx->direct_seq = 0; (void)hipStreamSynchronize(ctx->stream); return r; }
-    r = rec_collect(ctx);
     uint32_t late_cnt[2] = {0, 0};
-    if (r == C25519_LOST_PUBLICATION) {
-        // (r6) never observed (msm.hip wait_published): the small MSM once more, into the device slot, and the record by copy; the decode counters of the
-        // first kernel (still in d_flag) with it.  The staged scalars and the records of A_i, R_i, B are where they were.
-        slot_init(drec(ctx), m, nullptr, ctx->stream, g.c);
-        if ((r = msm_small_enqueue(ctx, dv + oC, d_pts, 1, m, g, drec(ctx), ctx->stream))) { (void)hipStreamSynchronize(ctx->stream); return r; }
-        if ((r = rec_collect(ctx))) return r;
-        HIPCHK(hipMemcpy(late_cnt, cnt, 8, hipMemcpyDeviceToHost));
-        ctx->err.clear();
-    }
+    r = msm_call_run(ctx, [&](bool allow_direct, msm_call &call) -> int32_t {
+        if (allow_direct) { call.seq = publish_next_seq(ctx); call.extra = cnt; }
+        else {
+            // (r6) a lost publication, never observed (msm.hip wait_published): the small MSM once more, into the device slot, and the record by copy; the decode
+            // counters of the first kernel (still in d_flag; the stream has drained) are read here.  The staged scalars and the records of A_i, R_i, B are where they were.
+            HIPCHK(hipMemcpy(late_cnt, cnt, 8, hipMemcpyDeviceToHost));
+            slot_init(drec(ctx), m, nullptr, ctx->stream, g.c);
+        }
+        const int32_t q = msm_small_enqueue(ctx, call, dv + oC, d_pts, 1, m, g, drec(ctx), ctx->stream);
+        if (q) (void)hipStreamSynchronize(ctx->stream);          // (the kernels ahead may still be reading the staging buffer)
+        return q;
+    });
     if (r) return r;
     HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
     ge_p3 R;

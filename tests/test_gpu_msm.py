@@ -607,3 +607,54 @@ def test_mid_path_lost_publication_is_recovered(orc):
     """) % (ROOT, ROOT)
     r = subprocess.run(util.child_argv(code), env=util.tune_env(C25519_FAULT_LOSE_PUBLICATION="3", C25519_PUBLISH_SPIN_US="1000"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-4000:])
+
+
+def test_small_path_lost_publication_is_recovered(orc):
+    """The small path's three recovery sites (c25519_msm_vartime_dev, c25519_msm_vartime below 6144 terms, and the host-assisted verify_batch of up to 128
+    signatures, whose re-run reads the decode counters late): with every third publication dropped (tuning build) each MSM gives the oracle's (sum x_i y_i) B and
+    each batch its verdict, on the direct run and on the recovered one alike; every call publishes once and every third is re-run."""
+    import subprocess, textwrap
+    code = textwrap.dedent("""
+        import os, sys, faulthandler
+        faulthandler.dump_traceback_later(300, exit=True)
+        sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, "tests"))
+        import numpy as np, torch
+        import curve25519_dalek_amd as pkg, util
+        from oracle import orc
+        L = util.L
+        OK, NONE, SCALAR_FORMAT, VERIFY = 0, 1, 2, 3
+        eng = pkg.Engine(0)
+        calls = 0
+        # MSM on raw points: one block, several blocks, the 6-bit windows, the path's last size -- device pointers and host pointers
+        for n in (1, 300, 1025, 6143):
+            x = util.rand_scalars(15 + n, n); y = util.rand_scalars(16 + n, n)
+            raw = eng.mul_base_batch(y, out_fmt=2)
+            tot = sum(int.from_bytes(a.tobytes(), "little") * int.from_bytes(b.tobytes(), "little") for a, b in zip(x, y)) %% L
+            want = orc.ed_compress(orc.ed_mul_base(tot.to_bytes(32, "little")))
+            dx, dr = torch.from_numpy(x).cuda(), torch.from_numpy(raw).cuda()
+            for rep in range(3):
+                st, got = eng.msm_vartime_t(dx, dr, in_fmt=2, out_fmt=0)
+                assert st == 0 and got == want, ("dev", n, rep)
+            for rep in range(3):
+                st, got = eng.msm_vartime(x, raw, in_fmt=2, out_fmt=0)
+                assert st == 0 and got == want, ("host", n, rep)
+            calls += 6
+        # verify_batch, host pointers: the verdicts that live in the decode counters (a bad key, a bad R) and on the host (a non-canonical s)
+        undecodable = (2).to_bytes(32, "little")
+        for n in (4, 128):
+            seeds = util.rand_bytes(3000 + n, n); msgs = util.rand_bytes(3001 + n, n, 41)
+            pks, sigs = orc.ed25519_keygen_sign_batch(seeds, msgs, threads=2)
+            M = [msgs[i].tobytes() for i in range(n)]; S = [sigs[i].tobytes() for i in range(n)]; P = [pks[i].tobytes() for i in range(n)]
+            bad_r = list(S); bad_r[n - 1] = undecodable + S[n - 1][32:]
+            bad_key = list(P); bad_key[n // 2] = undecodable
+            b = bytearray(S[1]); b[63] |= 0x20; bad_s = list(S); bad_s[1] = bytes(b)          # s >= 2^253
+            for z_mode in (1, 0):
+                for sg, pk, verdict in ((S, P, OK), (bad_r, P, VERIFY), (S, bad_key, NONE), (bad_s, P, SCALAR_FORMAT)):
+                    for rep in range(3):
+                        assert eng.verify_batch(M, sg, pk, z_mode) == verdict, (n, z_mode, verdict, rep)
+                    calls += 3
+        assert eng.counter(2) == calls and eng.counter(1) == eng.counter(2) // 3, (calls, eng.counter(2), eng.counter(1))
+        print("ok")
+    """) % (ROOT, ROOT)
+    r = subprocess.run(util.child_argv(code), env=util.tune_env(C25519_FAULT_LOSE_PUBLICATION="3", C25519_PUBLISH_SPIN_US="1000"), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-4000:])
