@@ -1,0 +1,276 @@
+// Segmented variable-time multiscalar multiplication: MANY independent sums  out[s] = sum_i scalars[i] * points[i]  over the segments
+// [seg_off[s], seg_off[s+1]) of one flat array of terms, in one call (traits.rs:249 VartimeMultiscalarMul, edwards.rs:1002-1031,
+// ristretto.rs:984 -- once per segment).  DESIGN.md section 3.13.
+//
+//   c25519_msm_vartime_segments_dev / c25519_msm_vartime_segments
+//
+// Straus with the doubling chain shared by the terms of a segment (scalar_mul/straus.rs:159-200), one LANE per segment:
+//   k_mid_seg_tables   one lane per term: decodes the point, writes its ok byte, the table {1 .. 8} P as eight 160-byte ProjectiveNiels
+//                      records (Y+X, Y-X, Z, 2dT) and the 64 signed radix-16 digits of the scalar (scalar.rs:1019-1051), raises the bit-255 flag
+//   k_mid_seg_straus   one lane per segment of at most C25519_MSM_SEGMENT_DIRECT_MAX terms: acc = 16 acc per window, then + / - entry |d| of
+//                      every term whose digit d is not zero.  Complete formulas (edwards.rs:797): no special case for equal, opposite or
+//                      identity operands.  The sum leaves as a raw 160-byte point.
+// Compressed outputs go through c25519_compress_batch_dev (no second inversion here).  Segments longer than the direct maximum run through
+// c25519_msm_partial_dev, one call each, and their sums are placed beside the others before that finishing step.
+// The scalars are public by contract (a *_vartime entry point): branches and table addresses depend on their digits.  Every loop bound comes
+// from the offsets the host validated; the kernels wait for nothing and use no atomics (the two verdict words are set by plain stores of 1).
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <string.h>
+#include <vector>
+#include "../../include/c25519_hip.h"
+#include "devio.h"
+#include "kernels.h"
+#include "ctx.h"
+#include "ffi.h"
+#include "knobs.h"
+#include "capi_util.h"
+
+using namespace c25519;
+
+namespace c25519 {
+
+constexpr int SEG_ENT = 8, SEG_ENT_Q = 10;                  // table entries per term; 16-byte pieces per entry (160 bytes)
+constexpr int SEG_DIG = 64;                                 // digit bytes per term (1280 + 64 = 1344 bytes per term, and its ok byte)
+enum { SEG_FLAG_NONE = 0, SEG_FLAG_BIT255 = 1 };            // the two verdict words at d_flag
+
+// entry e (0 .. 7 = 1 P .. 8 P) of term i: ten consecutive 16-byte pieces
+__device__ __forceinline__ void seg_tab_store(uint4 *tab, u64 i, int e, const ge_cached &c) {
+    u32 t[40];
+    for (int k = 0; k < 10; k++) { t[k] = c.YpX.v[k]; t[10 + k] = c.YmX.v[k]; t[20 + k] = c.Z.v[k]; t[30 + k] = c.T2d.v[k]; }
+    uint4 *q = tab + (i * SEG_ENT + (u64)e) * SEG_ENT_Q;
+    for (int k = 0; k < SEG_ENT_Q; k++) q[k] = make_uint4(t[4 * k], t[4 * k + 1], t[4 * k + 2], t[4 * k + 3]);
+}
+__device__ __forceinline__ ge_cached seg_tab_load(const uint4 *tab, u64 i, u32 e) {
+    const uint4 *q = tab + (i * SEG_ENT + (u64)e) * SEG_ENT_Q;
+    u32 t[40];
+    for (int k = 0; k < SEG_ENT_Q; k++) { const uint4 v = q[k]; t[4 * k] = v.x; t[4 * k + 1] = v.y; t[4 * k + 2] = v.z; t[4 * k + 3] = v.w; }
+    ge_cached c;
+    for (int k = 0; k < 10; k++) { c.YpX.v[k] = t[k]; c.YmX.v[k] = t[10 + k]; c.Z.v[k] = t[20 + k]; c.T2d.v[k] = t[30 + k]; }
+    return c;
+}
+
+// Terms [t0, t0 + cnt) of the call -> records 0 .. cnt - 1 of the pass: tok[i], tab[i], dig[i].  IN: 0 CompressedEdwardsY (ZIP-215 decoder),
+// 1 CompressedRistretto, 2 raw 160-byte (trusted).
+template <int IN>
+__global__ void __launch_bounds__(256) k_mid_seg_tables(const uint8_t *__restrict__ scalars, const uint8_t *__restrict__ points, u64 t0, u64 cnt,
+                                                        uint4 *__restrict__ tab, uint4 *__restrict__ dig, uint8_t *__restrict__ tok, u32 *__restrict__ flags) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const u64 g = t0 + i;
+    ge_p3 P;
+    bool good = true;
+    if (IN == 2) P = raw160_load(points, g);
+    else { u32 w[8]; load8(points, g, w); good = IN == 0 ? ge_decompress(P, w) : ris_decompress(P, w); }
+    tok[i] = good ? 1 : 0;
+    // {1 .. 8} P by repeated addition of P (window.rs:97-104)
+    const ge_cached c1 = ge_p3_to_cached(P);
+    seg_tab_store(tab, i, 0, c1);
+    ge_p3 acc = P;
+#pragma unroll 1
+    for (int j = 1; j < SEG_ENT; j++) {
+        acc = ge_p1p1_to_p3(ge_add_cached(acc, c1));
+        seg_tab_store(tab, i, j, ge_p3_to_cached(acc));
+    }
+    // digits: nibble_k(s') - 8 with s' = s + 0x0888...8, the top nibble left unsigned (0 .. 8), scalar.rs:1019-1051.  A scalar with bit 255
+    // set fails the call; its digits are taken from the low 255 bits so that every digit stays within the table.
+    u32 s[8];
+    load8(scalars, g, s);
+    if (s[7] >> 31) flags[SEG_FLAG_BIT255] = 1u;
+    s[7] &= 0x7fffffffu;
+    {
+        u64 carry = 0;
+        for (int k = 0; k < 8; k++) { const u64 v = (u64)s[k] + (k == 7 ? 0x08888888u : 0x88888888u) + carry; s[k] = (u32)v; carry = v >> 32; }
+    }
+    u32 d[16];                                              // 64 signed bytes, digit k in byte k
+    for (int k = 0; k < 16; k++) {
+        const u32 h = s[k >> 1] >> ((k & 1) * 16);
+        u32 word = 0;
+        for (int b = 0; b < 4; b++) {
+            const int nib = (int)((h >> (4 * b)) & 15u);
+            const int dg = (4 * k + b == 63) ? nib : nib - 8;
+            word |= ((u32)dg & 0xffu) << (8 * b);
+        }
+        d[k] = word;
+    }
+    uint4 *dq = dig + 4 * i;
+    for (int k = 0; k < 4; k++) dq[k] = make_uint4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
+}
+
+// Segments [s0, s0 + cnt) of the call, whose terms are records [seg_off[s] - t0, seg_off[s + 1] - t0) of the pass (nt records).  A segment
+// that is longer than dmax or does not lie within the records is left alone (the driver puts none into a pass).
+__global__ void __launch_bounds__(256) k_mid_seg_straus(const u64 *__restrict__ seg_off, u64 s0, u64 cnt, u64 t0, u64 nt, u32 dmax, const uint4 *__restrict__ tab,
+                                                        const int8_t *__restrict__ dig, const uint8_t *__restrict__ tok, uint8_t *__restrict__ out_raw,
+                                                        uint8_t *__restrict__ ok, u32 *__restrict__ flags) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const u64 s = s0 + i, a = seg_off[s], b = seg_off[s + 1];
+    if (a < t0 || b < a || b - t0 > nt || b - a > (u64)dmax) return;
+    const u64 lo = a - t0;
+    const u32 len = (u32)(b - a);
+    u32 good = 1;
+    for (u32 j = 0; j < len; j++) good &= (u32)tok[lo + j];
+    ge_p3 acc = ge_identity();
+#pragma unroll 1
+    for (int w = SEG_DIG - 1; w >= 0; w--) {
+        if (w != SEG_DIG - 1) acc = ge_mul_by_pow_2(acc, 4);
+#pragma unroll 1
+        for (u32 j = 0; j < len; j++) {
+            const int dg = (int)dig[(lo + j) * SEG_DIG + (u64)w];
+            if (dg != 0) {
+                const bool neg = dg < 0;
+                const u32 mag = (u32)(neg ? -dg : dg);                      // 1 .. 8
+                const ge_cached c = seg_tab_load(tab, lo + j, (mag - 1u) & 7u);
+                acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_cached_cneg(c, neg)));
+            }
+        }
+        ge_pin(acc);
+    }
+    raw160_store(out_raw, s, acc);
+    ok[s] = (uint8_t)good;
+    if (!good) flags[SEG_FLAG_NONE] = 1u;
+}
+
+}  // namespace c25519
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+static inline size_t seg_al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// the two constants of the header; the tuning build reads other values for an A/B run (knobs.h)
+static uint64_t seg_direct_max() { static const uint64_t v = (uint64_t)std::max<long long>(1, C25519_KNOB_LL("SEG_DIRECT_MAX", C25519_MSM_SEGMENT_DIRECT_MAX)); return v; }
+static uint64_t seg_pass_terms() {
+    static const uint64_t v = std::max<uint64_t>((uint64_t)std::max<long long>(1, C25519_KNOB_LL("SEG_PASS_TERMS", C25519_MSM_SEGMENT_PASS_TERMS)), seg_direct_max());
+    return v;
+}
+
+static int32_t seg_check(c25519_ctx *ctx, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m, int out_fmt) {
+    const bool pair = in_fmt == C25519_FMT_EDWARDS_Y ? ed_fmt_ok(out_fmt)
+                    : in_fmt == C25519_FMT_RISTRETTO ? ris_fmt_ok(out_fmt)
+                    : in_fmt == C25519_FMT_RAW160 && (ed_fmt_ok(out_fmt) || out_fmt == C25519_FMT_RISTRETTO);
+    if (!pair) return bad_arg(ctx, "msm_vartime_segments: in_fmt and out_fmt must belong to one group");
+    if (m >= 0xffffffffull) return bad_arg(ctx, "msm_vartime_segments: m must be below 2^32 - 1");
+    if (n >= (1ull << 40)) return bad_arg(ctx, "msm_vartime_segments: n must be < 2^40");
+    if (m == 0) return C25519_OK;
+    if (!seg_off || seg_off[0] != 0 || seg_off[m] != n) return bad_arg(ctx, "msm_vartime_segments: seg_off must run from 0 to n");
+    for (uint64_t s = 0; s < m; s++)
+        if (seg_off[s + 1] < seg_off[s]) return bad_arg(ctx, "msm_vartime_segments: seg_off must be non-decreasing");
+    return C25519_OK;
+}
+
+struct seg_pass { uint64_t s0, s1; };                       // segments [s0, s1): all direct, terms [seg_off[s0], seg_off[s1])
+
+// The whole call on device inputs.  h_out / h_ok (host form; may be null): where d_out / d_ok are copied before the one synchronisation.
+// seg_off has been checked (seg_check) and m > 0.
+static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m, int out_fmt,
+                       uint8_t *d_out, uint8_t *d_ok, uint8_t *h_out, uint8_t *h_ok) {
+    hipStream_t st = ctx->stream;
+    const size_t pb = point_bytes(in_fmt), ob = point_bytes(out_fmt);
+    const uint64_t dmax = seg_direct_max(), ptmax = seg_pass_terms();
+    // the passes: runs of direct segments of at most ptmax terms, cut at segment boundaries and at the long segments
+    std::vector<seg_pass> passes;
+    std::vector<uint64_t> longs;
+    uint64_t maxt = 0;
+    {
+        uint64_t s0 = 0, terms = 0;
+        auto close = [&](uint64_t s1) { if (s1 > s0) { passes.push_back({s0, s1}); maxt = std::max(maxt, terms); } terms = 0; };
+        for (uint64_t s = 0; s < m; s++) {
+            const uint64_t len = seg_off[s + 1] - seg_off[s];
+            if (len > dmax) { close(s); s0 = s + 1; longs.push_back(s); continue; }
+            if (terms + len > ptmax) { close(s); s0 = s; }
+            terms += len;
+        }
+        close(m);
+    }
+    // long segments first, each through the single-MSM path (it synchronises and uses workspaces of its own: nothing of this call is queued yet)
+    std::vector<uint8_t> long_sum(longs.size() * 160), long_ok(longs.size(), 1);
+    bool long_none = false;
+    for (size_t k = 0; k < longs.size(); k++) {
+        const uint64_t a = seg_off[longs[k]], len = seg_off[longs[k] + 1] - a;
+        const int32_t r = c25519_msm_partial_dev(ctx, d_scalars + a * 32, d_points + a * pb, len, in_fmt, long_sum.data() + 160 * k);
+        if (r == C25519_NONE) {                            // Option::None of this sum alone; its output is unspecified: the identity
+            long_ok[k] = 0; long_none = true;
+            memset(long_sum.data() + 160 * k, 0, 160);
+            long_sum[160 * k + 40] = 1; long_sum[160 * k + 80] = 1;
+        } else if (r) return r;
+    }
+    // tmp_f: seg_off | raw sums (compressed output only) | ok (without d_ok) | tables | digits | term ok bytes
+    const size_t b_off = seg_al256((m + 1) * 8), b_sum = out_fmt == C25519_FMT_RAW160 ? 0 : seg_al256(m * 160), b_ok = d_ok ? 0 : seg_al256(m);
+    const size_t b_tab = seg_al256(maxt * SEG_ENT * SEG_ENT_Q * 16), b_dig = seg_al256(maxt * SEG_DIG), b_tok = seg_al256(maxt);
+    int32_t r;
+    if ((r = ctx_reserve(ctx, ctx->tmp_f, b_off + b_sum + b_ok + b_tab + b_dig + b_tok + 256))) return r;
+    uint8_t *base = (uint8_t *)ctx->tmp_f.p;
+    uint64_t *d_off = (uint64_t *)base;
+    uint8_t *sums = out_fmt == C25519_FMT_RAW160 ? d_out : base + b_off;
+    uint8_t *okbuf = d_ok ? d_ok : base + b_off + b_sum;
+    uint4 *tab = (uint4 *)(base + b_off + b_sum + b_ok);
+    uint8_t *dig = base + b_off + b_sum + b_ok + b_tab, *tok = dig + b_dig;
+    uint32_t *flags = (uint32_t *)ctx->d_flag;
+    uint32_t *verdict = (uint32_t *)ctx->h_msm;           // pinned
+    auto enqueue = [&]() -> int32_t {
+        HIPCHK(hipMemsetAsync(flags, 0, 8, st));
+        HIPCHK(hipEventRecord(ctx->ev0, st));
+        HIPCHK(hipMemcpyAsync(d_off, seg_off, (m + 1) * 8, hipMemcpyHostToDevice, st));
+        ctx->kname[0] = "c25519::k_mid_seg_straus (one lane per segment, the doubling chain shared by its terms)";
+        for (const seg_pass &p : passes) {
+            const uint64_t t0 = seg_off[p.s0], nt = seg_off[p.s1] - t0, ns = p.s1 - p.s0;
+            if (nt) {
+                const dim3 g(div_up(nt, 256)), b(256);
+                if (in_fmt == C25519_FMT_EDWARDS_Y) hipLaunchKernelGGL(k_mid_seg_tables<0>, g, b, 0, st, d_scalars, d_points, t0, nt, tab, (uint4 *)dig, tok, flags);
+                else if (in_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_mid_seg_tables<1>, g, b, 0, st, d_scalars, d_points, t0, nt, tab, (uint4 *)dig, tok, flags);
+                else hipLaunchKernelGGL(k_mid_seg_tables<2>, g, b, 0, st, d_scalars, d_points, t0, nt, tab, (uint4 *)dig, tok, flags);
+                HIPCHK(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_mid_seg_straus, dim3(div_up(ns, 256)), dim3(256), 0, st, (const u64 *)d_off, p.s0, ns, t0, nt, (u32)dmax, (const uint4 *)tab,
+                               (const int8_t *)dig, (const uint8_t *)tok, sums, okbuf, flags);
+            HIPCHK(hipGetLastError());
+        }
+        for (size_t k = 0; k < longs.size(); k++) {
+            HIPCHK(hipMemcpyAsync(sums + longs[k] * 160, long_sum.data() + 160 * k, 160, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(okbuf + longs[k], long_ok.data() + k, 1, hipMemcpyHostToDevice, st));
+        }
+        if (out_fmt != C25519_FMT_RAW160) {
+            const int32_t q = c25519_compress_batch_dev(ctx, sums, m, out_fmt, d_out);
+            if (q) return q;
+        }
+        HIPCHK(hipEventRecord(ctx->ev1, st));
+        HIPCHK(hipMemcpyAsync(verdict, flags, 8, hipMemcpyDeviceToHost, st));
+        if (h_out) HIPCHK(hipMemcpyAsync(h_out, d_out, m * ob, hipMemcpyDeviceToHost, st));
+        if (h_ok) HIPCHK(hipMemcpyAsync(h_ok, okbuf, m, hipMemcpyDeviceToHost, st));
+        return C25519_OK;
+    };
+    r = enqueue();
+    if (r) { (void)hipStreamSynchronize(st); return r; }   // no queued copy still reads host memory after the return
+    HIPCHK(hipStreamSynchronize(st));
+    if (verdict[SEG_FLAG_BIT255]) return bad_arg(ctx, "msm: a scalar has bit 255 set (Scalar invariant #1 violated)");
+    return (verdict[SEG_FLAG_NONE] || long_none) ? C25519_NONE : C25519_OK;
+}
+
+EXPORT int32_t c25519_msm_vartime_segments_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const uint64_t *seg_off,
+                                               uint64_t m, int out_fmt, uint8_t *d_out, uint8_t *d_ok) {
+    HIPCHK(hipSetDevice(ctx->device));
+    int32_t r;
+    if ((r = seg_check(ctx, n, in_fmt, seg_off, m, out_fmt))) return r;
+    if (m == 0) return C25519_OK;
+    return seg_run(ctx, d_scalars, d_points, n, in_fmt, seg_off, m, out_fmt, d_out, d_ok, nullptr, nullptr);
+}
+
+EXPORT int32_t c25519_msm_vartime_segments(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m,
+                                           int out_fmt, uint8_t *out, uint8_t *ok) {
+    HIPCHK(hipSetDevice(ctx->device));
+    int32_t r;
+    if ((r = seg_check(ctx, n, in_fmt, seg_off, m, out_fmt))) return r;
+    if (m == 0) return C25519_OK;
+    const size_t pb = point_bytes(in_fmt), ob = point_bytes(out_fmt);
+    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * pb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, seg_al256(m * ob) + m + 16)))
+        return r;
+    ffi_small_begin(ctx);
+    uint8_t *d_s = (uint8_t *)ctx->tmp_a.p, *d_p = (uint8_t *)ctx->tmp_b.p, *d_out = (uint8_t *)ctx->tmp_c.p, *d_ok = d_out + seg_al256(m * ob);
+    if (n) {
+        hipError_t e = hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_p, points, n * pb, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return c25519_fail(ctx, e, "hipMemcpyAsync(inputs)"); }
+    }
+    r = seg_run(ctx, d_s, d_p, n, in_fmt, seg_off, m, out_fmt, d_out, d_ok, out, ok);
+    if (r < 0) (void)hipStreamSynchronize(ctx->stream);    // (an early error: the uploads may still be reading the caller's memory)
+    ffi_small_end(ctx, n * (32 + pb) + (m + 1) * 8, m * ob + (ok ? m : 0));
+    return r;
+}

@@ -4,6 +4,7 @@ error behaviour), batched, on top of Engine.  Reference entry points mirrored:
   EdwardsPoint::mul_base                      curve25519-dalek/src/edwards.rs:918
   EdwardsPoint::vartime_multiscalar_mul       curve25519-dalek/src/traits.rs:249 / edwards.rs:1002
   RistrettoPoint::vartime_multiscalar_mul     curve25519-dalek/src/ristretto.rs:984
+  EdwardsPoint / RistrettoPoint::vartime_multiscalar_mul, many independent sums in one call   (vartime_multiscalar_mul_many)
   CompressedEdwardsY::decompress / compress   edwards.rs:211 / :615
   x25519                                      x25519-dalek/src/x25519.rs:390
   verify_batch                                ed25519-dalek/src/batch.rs:146
@@ -100,6 +101,12 @@ class EdwardsPoint:
         eng = engine or default_engine()
         st, out = eng.msm_vartime(_cat(scalars, 32), _cat(points, 32), _e.FMT_EDWARDS_Y, _e.FMT_EDWARDS_Y)
         return None if st == _e.NONE else out
+
+    @staticmethod
+    def vartime_multiscalar_mul_many(scalar_lists, point_lists, engine=None):
+        """[vartime_multiscalar_mul(scalar_lists[k], point_lists[k])] for every k in one call: CompressedEdwardsY bytes, or None where a
+        point of that sum does not decompress.  Unequal lengths inside a pair raise, as in the single form."""
+        return _msm_many(scalar_lists, point_lists, _e.FMT_EDWARDS_Y, engine)
 
     @staticmethod
     def vartime_double_scalar_mul_basepoint(a, A, b, engine=None):
@@ -243,6 +250,10 @@ class RistrettoPoint:
         st, out = eng.msm_vartime(_cat(scalars, 32), _cat(points, 32), _e.FMT_RISTRETTO, _e.FMT_RISTRETTO)
         return None if st == _e.NONE else out
 
+    @staticmethod
+    def vartime_multiscalar_mul_many(scalar_lists, point_lists, engine=None):
+        """[vartime_multiscalar_mul(scalar_lists[k], point_lists[k])] for every k in one call: CompressedRistretto bytes, or None"""
+        return _msm_many(scalar_lists, point_lists, _e.FMT_RISTRETTO, engine)
 
     @staticmethod
     def from_uniform_bytes(inputs, engine=None):
@@ -350,6 +361,16 @@ class RistrettoPoint:
         eng = engine or default_engine()
         out, ok = eng.double_base_batch(_cat(a, 32), _cat(A, 32), _cat(b, 32), _e.FMT_RISTRETTO, _e.FMT_RISTRETTO)
         return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+
+def _msm_many(scalar_lists, point_lists, fmt, engine):
+    if len(scalar_lists) != len(point_lists) or any(len(s) != len(p) for s, p in zip(scalar_lists, point_lists)):
+        raise AssertionError("vartime_multiscalar_mul: scalars and points must have equal length")
+    off = np.zeros(len(scalar_lists) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(s) for s in scalar_lists], dtype=np.uint64)
+    eng = engine or default_engine()
+    _, out, ok = eng.msm_vartime_segments(_cat([x for s in scalar_lists for x in s], 32), _cat([x for p in point_lists for x in p], 32), off, fmt, fmt)
+    return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
 
 
 def _group_add(ps, qs, op, fmt, what, engine):

@@ -161,6 +161,8 @@ _SIGS = {
     "c25519_point_eq_batch": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp, _vp]),
     "c25519_point_sum_segments_dev": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_point_sum_segments": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_msm_vartime_segments_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_msm_vartime_segments": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_microbench": (C.c_double, [_vp, C.c_int, C.c_int]),
     "c25519_selftest_field": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _u64, _vp]),
     "c25519_selftest_scalar": (_i32, [_vp, C.c_int, _vp, _vp, _u64, _vp]),
@@ -197,6 +199,8 @@ def load_library():
 
 _PT = {FMT_EDWARDS_Y: 32, FMT_RISTRETTO: 32, FMT_RAW160: 160}
 PARTIAL_RECORD_BYTES = 9024      # C25519_PARTIAL_RECORD_BYTES
+MSM_SEGMENT_DIRECT_MAX = 64      # C25519_MSM_SEGMENT_DIRECT_MAX: the longest segment msm_vartime_segments runs one per lane
+MSM_SEGMENT_PASS_TERMS = 1 << 18     # C25519_MSM_SEGMENT_PASS_TERMS: most terms whose tables are resident at once
 
 
 def _np8(x, width):
@@ -669,6 +673,25 @@ class Engine:
                                                               out.data_ptr(), ok.data_ptr()), (OK, NONE))
         return st, out, ok
 
+    def msm_vartime_segments_t(self, scalars, points, seg_off, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):
+        """many independent vartime MSMs: out[s] = sum scalars[i] * points[i] over [seg_off[s], seg_off[s+1]).  scalars (n, 32), points
+        (n, 32|160) uint8 CUDA tensors; seg_off m + 1 offsets on the HOST (a sequence or a CPU tensor: the lengths are public and the host
+        routes by them) -> (status OK | NONE, (m, 32|160), ok (m,))"""
+        n = self._t(scalars, 32)
+        assert self._t(points, _PT.get(in_fmt, 32)) == n
+        if hasattr(seg_off, "is_cuda"):
+            assert not seg_off.is_cuda, "seg_off stays on the host"
+            seg_off = seg_off.numpy()
+        off = np.ascontiguousarray(np.asarray(seg_off, dtype=np.uint64).reshape(-1))
+        assert off.shape[0] >= 1
+        m = off.shape[0] - 1
+        out = self.torch.empty((m, _PT.get(out_fmt, 32)), dtype=self.torch.uint8, device=self.device)
+        ok = self.torch.empty((m,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_msm_vartime_segments_dev(self.ctx, scalars.data_ptr(), points.data_ptr(), n, in_fmt, off.ctypes.data, m, out_fmt,
+                                                                out.data_ptr(), ok.data_ptr()), (OK, NONE))
+        return st, out, ok
+
     # -- host-buffer API (numpy in / numpy out) ---------------------------------------------------
     @staticmethod
     def _out(out, n, width):
@@ -1120,6 +1143,22 @@ class Engine:
         self._bind_stream()
         st = self._chk(self.lib.c25519_point_sum_segments(self.ctx, a.ctypes.data, a.shape[0], in_fmt, off.ctypes.data, m, out_fmt, out.ctypes.data,
                                                           ok.ctypes.data), (OK, NONE))
+        return st, out, ok
+
+    def msm_vartime_segments(self, scalars, points, seg_off, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):
+        """many independent vartime MSMs in one call (optional_multiscalar_mul per segment, edwards.rs:1002-1031 / ristretto.rs:984):
+        out[s] = sum scalars[i] * points[i] over [seg_off[s], seg_off[s+1]) -> (status OK | NONE, (m, 32|160), ok (m,)); ok[s] = 0 where a
+        point of segment s does not decode"""
+        s = _np8(scalars, 32) if len(scalars) else np.zeros((0, 32), np.uint8)
+        a = _np8(points, _PT.get(in_fmt, 32)) if len(points) else np.zeros((0, _PT.get(in_fmt, 32)), np.uint8)
+        assert s.shape[0] == a.shape[0]
+        off = np.ascontiguousarray(np.asarray(seg_off, dtype=np.uint64).reshape(-1))
+        assert off.shape[0] >= 1
+        m = off.shape[0] - 1
+        out = np.empty((m, _PT.get(out_fmt, 32)), np.uint8); ok = np.empty((m,), np.uint8)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_msm_vartime_segments(self.ctx, s.ctypes.data, a.ctypes.data, s.shape[0], in_fmt, off.ctypes.data, m, out_fmt,
+                                                            out.ctypes.data, ok.ctypes.data), (OK, NONE))
         return st, out, ok
 
     def scalar_invert_batch(self, scalars):

@@ -244,6 +244,40 @@ int32_t c25519_msm_vartime(c25519_ctx *ctx, const uint8_t *scalars, const uint8_
 int32_t c25519_msm_partial_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, uint8_t *out160);
 int32_t c25519_fold_partials(c25519_ctx *ctx, const uint8_t *partials160, uint64_t count, int out_fmt, uint8_t *out);
 
+/* MANY independent sums in one call: out[s] = sum of scalars[i] * points[i] for i in [seg_off[s], seg_off[s+1]), s < m -- one
+ * VartimeMultiscalarMul::optional_multiscalar_mul (traits.rs:249; edwards.rs:1002-1031, ristretto.rs:984) per segment: Schnorr / DLEQ /
+ * Pedersen-opening checks of a few terms each, thousands at a time, whose verdicts must stay separate.  Variable time: the scalars are
+ * public by contract, as for c25519_msm_vartime.  (Secret scalars: c25519_mul_batch_dev on a constant-time context, then
+ * c25519_point_sum_segments_dev.)
+ *   - scalars n x 32, points n x 32 | 160, out m x 32 | 160, ok m bytes (may be NULL): HOST pointers in the un-suffixed form, DEVICE
+ *     pointers in the _dev form.  seg_off is a HOST array in BOTH forms -- the lengths are public and the host routes by them: m + 1
+ *     non-decreasing values with seg_off[0] = 0 and seg_off[m] = n, anything else returns -(hipErrorInvalidValue) before any launch.
+ *     m must be below 2^32 - 1; m == 0 returns C25519_OK.  An empty segment gives the identity.
+ *   - formats as for the group law below: in C25519_FMT_EDWARDS_Y -> out 0 or 2, in C25519_FMT_RISTRETTO -> out 1 or 2, in
+ *     C25519_FMT_RAW160 -> out 0, 1 or 2; any other pair returns -(hipErrorInvalidValue).  A RAW160 input is trusted to be a point;
+ *     compressed inputs decode as in c25519_decompress_batch.
+ *   - ok[s] = 0 iff some point of segment s does not decode (the reference's Option::None, per sum; out[s] is then unspecified).  The call
+ *     returns C25519_NONE if any segment failed and C25519_OK otherwise; the other segments are unaffected.
+ *   - a scalar with bit 255 set, anywhere, returns -(hipErrorInvalidValue) with the message of c25519_msm_vartime; scalars need not be
+ *     reduced mod l.
+ *   - both forms synchronise the context's stream once, at the end, to read the two verdict words.
+ *   - every out[s] is byte for byte what c25519_msm_vartime returns for that segment alone (canonical encodings); a RAW160 output is the
+ *     same point (equal under ct_eq), not the same limbs.
+ * Cost: segments of at most C25519_MSM_SEGMENT_DIRECT_MAX terms run one per GPU lane -- Straus with the doubling chain shared by the
+ * terms of the segment (scalar_mul/straus.rs:159-200), radix 16 -- so a wave of 64 consecutive segments costs what its LONGEST one costs:
+ * group segments of similar length next to each other.  A longer segment is not what this call is for, but is served: each runs as a
+ * c25519_msm_partial_dev of its own (tens of microseconds of latency apiece, one after the other).  The tables of at most
+ * C25519_MSM_SEGMENT_PASS_TERMS terms (1344 bytes per term) are resident at a time; more terms run as several passes, cut at segment
+ * boundaries.  tools/seg_msm_numbers.py times the call against one c25519_msm_vartime_dev per segment and against c25519_mul_batch_dev +
+ * c25519_point_sum_segments_dev. */
+#define C25519_MSM_SEGMENT_DIRECT_MAX 64       /* longest segment the segmented kernels take themselves */
+#define C25519_MSM_SEGMENT_PASS_TERMS 262144   /* most terms whose tables are resident at once (2^18: a 352 MB workspace) */
+int32_t c25519_msm_vartime_segments_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt,
+                                        const uint64_t *seg_off /* HOST, m + 1 */, uint64_t m, int out_fmt, uint8_t *d_out /* device, m x (32 | 160) */,
+                                        uint8_t *d_ok /* device, m bytes, may be NULL */);
+int32_t c25519_msm_vartime_segments(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m,
+                                    int out_fmt, uint8_t *out, uint8_t *ok);
+
 /* The same decomposition WITHOUT the partial sum ever visiting the host (what curve25519-dalek_amd/multi.py runs, one
  * process per GPU): c25519_msm_partial_record_dev only ENQUEUES on the context's stream and leaves a fixed-size RECORD in
  * device memory -- the window column sums of this rank's terms (the reference's `columns`, pippenger.rs:146-151, before
