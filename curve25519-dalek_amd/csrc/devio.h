@@ -163,4 +163,17 @@ __device__ __forceinline__ bool raw160_z_is_one(const uint8_t *in, u64 idx) {
     return (p[0] == 1) & ((p[1] | p[2] | p[3] | p[4]) == 0);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The point held by lane (this lane + off) of the wave: 40 words through __shfl_down (a lane whose source lies past lane 63 gets its own
+// point back).  What the wave-wide sums are folded with: for (off = 32; off > 0; off >>= 1) acc = add(acc, ge_shfl_down(acc, off))
+// leaves the total in lane 0 -- the additions are complete, so identity, equal and opposite operands need no special case.
+__device__ __forceinline__ ge_p3 ge_shfl_down(const ge_p3 &p, int off) {
+    ge_p3 o;
+    for (int i = 0; i < 10; i++) {
+        o.X.v[i] = __shfl_down(p.X.v[i], off, 64); o.Y.v[i] = __shfl_down(p.Y.v[i], off, 64);
+        o.Z.v[i] = __shfl_down(p.Z.v[i], off, 64); o.T.v[i] = __shfl_down(p.T.v[i], off, 64);
+    }
+    return o;
+}
+
 }  // namespace c25519

@@ -41,14 +41,7 @@ __global__ void __launch_bounds__(64) k_sum_p40(const u32 *__restrict__ in, u64 
         if (idx < m) acc = ge_add(acc, p40_load(in, idx));
     }
 #pragma unroll 1
-    for (int off = 32; off > 0; off >>= 1) {
-        ge_p3 o;
-        for (int i = 0; i < 10; i++) {
-            o.X.v[i] = __shfl_down(acc.X.v[i], off, 64); o.Y.v[i] = __shfl_down(acc.Y.v[i], off, 64);
-            o.Z.v[i] = __shfl_down(acc.Z.v[i], off, 64); o.T.v[i] = __shfl_down(acc.T.v[i], off, 64);
-        }
-        acc = ge_add(acc, o);
-    }
+    for (int off = 32; off > 0; off >>= 1) acc = ge_add(acc, ge_shfl_down(acc, off));
     if (threadIdx.x == 0) p40_store(out, blockIdx.x, acc);
 }
 

@@ -149,14 +149,7 @@ C25519_HD ge_p3 mid_add_cols(const ge_p3 &p, const ge_p3 &q) { return ge_add(p, 
 #endif
 __device__ __forceinline__ ge_p3 mid_wave_sum(ge_p3 acc) {      // complete additions across the 64 lanes; lane 0 ends with the total
 #pragma unroll 1
-    for (int off = 32; off > 0; off >>= 1) {
-        ge_p3 o;
-        for (int i = 0; i < 10; i++) {
-            o.X.v[i] = __shfl_down(acc.X.v[i], off, 64); o.Y.v[i] = __shfl_down(acc.Y.v[i], off, 64);
-            o.Z.v[i] = __shfl_down(acc.Z.v[i], off, 64); o.T.v[i] = __shfl_down(acc.T.v[i], off, 64);
-        }
-        acc = mid_add_cols(acc, o);
-    }
+    for (int off = 32; off > 0; off >>= 1) acc = mid_add_cols(acc, ge_shfl_down(acc, off));
     return acc;
 }
 // over-long lists (more than long_cap entries: skewed digits -- verify_batch's carry digit puts ~n/2 terms into ONE bucket, equal scalars do it in every window): one wave

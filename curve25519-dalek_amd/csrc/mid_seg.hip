@@ -2,7 +2,7 @@
 // [seg_off[s], seg_off[s+1]) of one flat array of terms, in one call (traits.rs:249 VartimeMultiscalarMul, edwards.rs:1002-1031,
 // ristretto.rs:984 -- once per segment).  DESIGN.md section 3.13.
 //
-//   c25519_msm_vartime_segments_dev / c25519_msm_vartime_segments
+//   c25519_msm_vartime_segments_dev / c25519_msm_vartime_segments / c25519_msm_vartime_segments_plan
 //
 // Straus with the doubling chain shared by the terms of a segment (scalar_mul/straus.rs:159-200), one LANE per segment:
 //   k_mid_seg_tables   one lane per term: decodes the point, writes its ok byte, the table {1 .. 8} P as eight 160-byte ProjectiveNiels
@@ -10,7 +10,10 @@
 //   k_mid_seg_straus   one lane per segment of at most C25519_MSM_SEGMENT_DIRECT_MAX terms: acc = 16 acc per window, then + / - entry |d| of
 //                      every term whose digit d is not zero.  Complete formulas (edwards.rs:797): no special case for equal, opposite or
 //                      identity operands.  The sum leaves as a raw 160-byte point.
-// Compressed outputs go through c25519_compress_batch_dev (no second inversion here).  Segments longer than the direct maximum run through
+//   k_mid_seg_wave     one WAVE per segment of at most C25519_MSM_SEGMENT_WAVE_MAX terms: lane l takes terms l, l + 64, l + 128, ... and runs
+//                      the same window loop over them; the 64 partial sums are folded across the wave with six shuffle rounds.  (The constant
+//                      is measured; the kernel itself is correct for any length.)
+// Compressed outputs go through c25519_compress_batch_dev (no second inversion here).  Segments longer than the wave maximum run through
 // c25519_msm_partial_dev, one call each, and their sums are placed beside the others before that finishing step.
 // The scalars are public by contract (a *_vartime entry point): branches and table addresses depend on their digits.  Every loop bound comes
 // from the offsets the host validated; the kernels wait for nothing and use no atomics (the two verdict words are set by plain stores of 1).
@@ -98,7 +101,7 @@ __global__ void __launch_bounds__(256) k_mid_seg_tables(const uint8_t *__restric
 }
 
 // Segments [s0, s0 + cnt) of the call, whose terms are records [seg_off[s] - t0, seg_off[s + 1] - t0) of the pass (nt records).  A segment
-// that is longer than dmax or does not lie within the records is left alone (the driver puts none into a pass).
+// that is longer than dmax or does not lie within the records is left alone (the longer ones of a pass belong to k_mid_seg_wave).
 __global__ void __launch_bounds__(256) k_mid_seg_straus(const u64 *__restrict__ seg_off, u64 s0, u64 cnt, u64 t0, u64 nt, u32 dmax, const uint4 *__restrict__ tab,
                                                         const int8_t *__restrict__ dig, const uint8_t *__restrict__ tok, uint8_t *__restrict__ out_raw,
                                                         uint8_t *__restrict__ ok, u32 *__restrict__ flags) {
@@ -131,32 +134,133 @@ __global__ void __launch_bounds__(256) k_mid_seg_straus(const u64 *__restrict__ 
     if (!good) flags[SEG_FLAG_NONE] = 1u;
 }
 
+// Wave w of the launch takes segment ids[w] (cnt ids: the pass's segments of more than dmax terms), whose terms are records
+// [seg_off[s] - t0, seg_off[s + 1] - t0) of the pass, as for k_mid_seg_straus.  Lane l handles terms l, l + 64, ... of the segment: the window
+// loop of k_mid_seg_straus over its own terms, then the 64 partial sums are folded (ge_shfl_down, complete additions: a lane without a term
+// holds the identity) and lane 0 stores the sum and the verdict.  Correct for any length >= 1.  The segment index, the offsets and every loop
+// bound are wave-uniform (readfirstlane: SGPRs); only the term predicate and the zero-digit skip depend on the lane.  No LDS, no barrier.
+__global__ void __launch_bounds__(256) k_mid_seg_wave(const u64 *__restrict__ seg_off, const u32 *__restrict__ ids, u32 cnt, u64 t0, u64 nt, const uint4 *__restrict__ tab,
+                                                      const int8_t *__restrict__ dig, const uint8_t *__restrict__ tok, uint8_t *__restrict__ out_raw,
+                                                      uint8_t *__restrict__ ok, u32 *__restrict__ flags) {
+    const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    if (wv >= cnt) return;
+    const u32 lane = threadIdx.x & 63u;
+    const u32 s = ids[wv];
+    const u64 a = seg_off[s], b = seg_off[(u64)s + 1];
+    if (a < t0 || b < a || b - t0 > nt || b - a > 0xffffffc0ull) return;
+    const u64 lo = a - t0;
+    const u32 len = (u32)(b - a), rounds = (len + 63u) >> 6;
+    u32 good = 1;
+    for (u32 r = 0; r < rounds; r++) {
+        const u32 j = 64u * r + lane;
+        if (j < len) good &= (u32)tok[lo + j];
+    }
+    ge_p3 acc = ge_identity();
+#pragma unroll 1
+    for (int w = SEG_DIG - 1; w >= 0; w--) {
+        if (w != SEG_DIG - 1) acc = ge_mul_by_pow_2(acc, 4);
+#pragma unroll 1
+        for (u32 r = 0; r < rounds; r++) {
+            const u32 j = 64u * r + lane;
+            if (j < len) {
+                const int dg = (int)dig[(lo + j) * SEG_DIG + (u64)w];
+                if (dg != 0) {
+                    const bool neg = dg < 0;
+                    const u32 mag = (u32)(neg ? -dg : dg);                  // 1 .. 8
+                    const ge_cached c = seg_tab_load(tab, lo + j, (mag - 1u) & 7u);
+                    acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_cached_cneg(c, neg)));
+                }
+            }
+        }
+        ge_pin(acc);
+    }
+#pragma unroll 1
+    for (int off = 32; off > 0; off >>= 1) acc = ge_add(acc, ge_shfl_down(acc, off));
+    const bool all_good = __all((int)good) != 0;
+    if (lane == 0) {
+        raw160_store(out_raw, s, acc);
+        ok[s] = all_good ? 1 : 0;
+        if (!all_good) flags[SEG_FLAG_NONE] = 1u;
+    }
+}
+
 }  // namespace c25519
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 static inline size_t seg_al256(size_t b) { return (b + 255) & ~(size_t)255; }
-// the two constants of the header; the tuning build reads other values for an A/B run (knobs.h)
+// the three constants of the header; the tuning build reads other values for an A/B run (knobs.h)
 static uint64_t seg_direct_max() { static const uint64_t v = (uint64_t)std::max<long long>(1, C25519_KNOB_LL("SEG_DIRECT_MAX", C25519_MSM_SEGMENT_DIRECT_MAX)); return v; }
-static uint64_t seg_pass_terms() {
-    static const uint64_t v = std::max<uint64_t>((uint64_t)std::max<long long>(1, C25519_KNOB_LL("SEG_PASS_TERMS", C25519_MSM_SEGMENT_PASS_TERMS)), seg_direct_max());
+static uint64_t seg_wave_max() {
+    static const uint64_t v = std::max<uint64_t>((uint64_t)std::max<long long>(1, C25519_KNOB_LL("SEG_WAVE_MAX", C25519_MSM_SEGMENT_WAVE_MAX)), seg_direct_max());
+    return v;
+}
+static uint64_t seg_pass_terms() {                          // at least the wave maximum: one segment always fits into a pass
+    static const uint64_t v = std::max<uint64_t>((uint64_t)std::max<long long>(1, C25519_KNOB_LL("SEG_PASS_TERMS", C25519_MSM_SEGMENT_PASS_TERMS)), seg_wave_max());
     return v;
 }
 
+// (ctx may be null: c25519_msm_vartime_segments_plan has none, and then only the code is returned)
+static int32_t seg_bad(c25519_ctx *ctx, const char *what) { return ctx ? bad_arg(ctx, what) : -(int32_t)hipErrorInvalidValue; }
+static int32_t seg_check_off(c25519_ctx *ctx, uint64_t n, const uint64_t *seg_off, uint64_t m) {
+    if (m >= 0xffffffffull) return seg_bad(ctx, "msm_vartime_segments: m must be below 2^32 - 1");
+    if (n >= (1ull << 40)) return seg_bad(ctx, "msm_vartime_segments: n must be < 2^40");
+    if (m == 0) return C25519_OK;
+    if (!seg_off || seg_off[0] != 0 || seg_off[m] != n) return seg_bad(ctx, "msm_vartime_segments: seg_off must run from 0 to n");
+    for (uint64_t s = 0; s < m; s++)
+        if (seg_off[s + 1] < seg_off[s]) return seg_bad(ctx, "msm_vartime_segments: seg_off must be non-decreasing");
+    return C25519_OK;
+}
 static int32_t seg_check(c25519_ctx *ctx, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m, int out_fmt) {
     const bool pair = in_fmt == C25519_FMT_EDWARDS_Y ? ed_fmt_ok(out_fmt)
                     : in_fmt == C25519_FMT_RISTRETTO ? ris_fmt_ok(out_fmt)
                     : in_fmt == C25519_FMT_RAW160 && (ed_fmt_ok(out_fmt) || out_fmt == C25519_FMT_RISTRETTO);
     if (!pair) return bad_arg(ctx, "msm_vartime_segments: in_fmt and out_fmt must belong to one group");
-    if (m >= 0xffffffffull) return bad_arg(ctx, "msm_vartime_segments: m must be below 2^32 - 1");
-    if (n >= (1ull << 40)) return bad_arg(ctx, "msm_vartime_segments: n must be < 2^40");
-    if (m == 0) return C25519_OK;
-    if (!seg_off || seg_off[0] != 0 || seg_off[m] != n) return bad_arg(ctx, "msm_vartime_segments: seg_off must run from 0 to n");
-    for (uint64_t s = 0; s < m; s++)
-        if (seg_off[s + 1] < seg_off[s]) return bad_arg(ctx, "msm_vartime_segments: seg_off must be non-decreasing");
-    return C25519_OK;
+    return seg_check_off(ctx, n, seg_off, m);
 }
 
-struct seg_pass { uint64_t s0, s1; };                       // segments [s0, s1): all direct, terms [seg_off[s0], seg_off[s1])
+// ---- routing: the one place that decides which kernel a segment gets and where the passes are cut ----
+//   len <= dmax   lane   (k_mid_seg_straus; empty segments too: they give the identity)
+//   len <= wmax   wave   (k_mid_seg_wave)
+//   longer        the single-MSM path, one c25519_msm_partial_dev each
+// A pass is a run of consecutive lane and wave segments of at most ptmax terms in all (ptmax >= wmax: one segment always fits); only the
+// single-MSM segments and the term count cut it.  The wave kernel of a pass runs over wave_ids[w0 .. w1).
+struct seg_pass { uint64_t s0, s1, w0, w1, lanes; };       // segments [s0, s1), terms [seg_off[s0], seg_off[s1]); `lanes` of them on the lane route
+struct seg_route {
+    uint64_t n_lane = 0, n_wave = 0, n_long = 0, n_pass = 0, maxt = 0;      // what c25519_msm_vartime_segments_plan reports
+    std::vector<seg_pass> passes;                           // the lists: only when asked for (seg_run)
+    std::vector<uint32_t> wave_ids;
+    std::vector<uint64_t> longs;
+};
+static void seg_plan(const uint64_t *seg_off, uint64_t m, bool lists, seg_route &R) {
+    const uint64_t dmax = seg_direct_max(), wmax = seg_wave_max(), ptmax = seg_pass_terms();
+    uint64_t s0 = 0, terms = 0, w0 = 0, lanes = 0;
+    auto close = [&](uint64_t s1) {
+        if (s1 > s0) {
+            R.n_pass++; R.maxt = std::max(R.maxt, terms);
+            if (lists) R.passes.push_back({s0, s1, w0, R.n_wave, lanes});
+        }
+        terms = 0; lanes = 0; w0 = R.n_wave;
+    };
+    for (uint64_t s = 0; s < m; s++) {
+        const uint64_t len = seg_off[s + 1] - seg_off[s];
+        if (len > wmax) { close(s); s0 = s + 1; R.n_long++; if (lists) R.longs.push_back(s); continue; }
+        if (terms + len > ptmax) { close(s); s0 = s; }
+        terms += len;
+        if (len > dmax) { R.n_wave++; if (lists) R.wave_ids.push_back((uint32_t)s); }     // s < m < 2^32 - 1: seg_check_off has bounded m
+        else { R.n_lane++; lanes++; }
+    }
+    close(m);
+}
+
+EXPORT int32_t c25519_msm_vartime_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[5]) {
+    if (m >= 0xffffffffull) return seg_bad(nullptr, "m");    // before seg_off[m] is read for n
+    int32_t r;
+    if ((r = seg_check_off(nullptr, (m && seg_off) ? seg_off[m] : 0, seg_off, m))) return r;
+    seg_route R;
+    seg_plan(seg_off, m, false, R);
+    plan[0] = R.n_lane; plan[1] = R.n_wave; plan[2] = R.n_long; plan[3] = R.n_pass; plan[4] = R.maxt;
+    return C25519_OK;
+}
 
 // The whole call on device inputs.  h_out / h_ok (host form; may be null): where d_out / d_ok are copied before the one synchronisation.
 // seg_off has been checked (seg_check) and m > 0.
@@ -164,22 +268,12 @@ static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
                        uint8_t *d_out, uint8_t *d_ok, uint8_t *h_out, uint8_t *h_ok) {
     hipStream_t st = ctx->stream;
     const size_t pb = point_bytes(in_fmt), ob = point_bytes(out_fmt);
-    const uint64_t dmax = seg_direct_max(), ptmax = seg_pass_terms();
-    // the passes: runs of direct segments of at most ptmax terms, cut at segment boundaries and at the long segments
-    std::vector<seg_pass> passes;
-    std::vector<uint64_t> longs;
-    uint64_t maxt = 0;
-    {
-        uint64_t s0 = 0, terms = 0;
-        auto close = [&](uint64_t s1) { if (s1 > s0) { passes.push_back({s0, s1}); maxt = std::max(maxt, terms); } terms = 0; };
-        for (uint64_t s = 0; s < m; s++) {
-            const uint64_t len = seg_off[s + 1] - seg_off[s];
-            if (len > dmax) { close(s); s0 = s + 1; longs.push_back(s); continue; }
-            if (terms + len > ptmax) { close(s); s0 = s; }
-            terms += len;
-        }
-        close(m);
-    }
+    const uint64_t dmax = seg_direct_max();
+    seg_route R;
+    seg_plan(seg_off, m, true, R);
+    const std::vector<seg_pass> &passes = R.passes;
+    const std::vector<uint64_t> &longs = R.longs;
+    const uint64_t maxt = R.maxt;
     // long segments first, each through the single-MSM path (it synchronises and uses workspaces of its own: nothing of this call is queued yet)
     std::vector<uint8_t> long_sum(longs.size() * 160), long_ok(longs.size(), 1);
     bool long_none = false;
@@ -192,13 +286,15 @@ static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
             long_sum[160 * k + 40] = 1; long_sum[160 * k + 80] = 1;
         } else if (r) return r;
     }
-    // tmp_f: seg_off | raw sums (compressed output only) | ok (without d_ok) | tables | digits | term ok bytes
-    const size_t b_off = seg_al256((m + 1) * 8), b_sum = out_fmt == C25519_FMT_RAW160 ? 0 : seg_al256(m * 160), b_ok = d_ok ? 0 : seg_al256(m);
+    // tmp_f: seg_off | segment ids of the wave route, pass after pass | raw sums (compressed output only) | ok (without d_ok) | tables | digits |
+    // term ok bytes
+    const size_t b_off = seg_al256((m + 1) * 8) + seg_al256(R.wave_ids.size() * 4), b_sum = out_fmt == C25519_FMT_RAW160 ? 0 : seg_al256(m * 160), b_ok = d_ok ? 0 : seg_al256(m);
     const size_t b_tab = seg_al256(maxt * SEG_ENT * SEG_ENT_Q * 16), b_dig = seg_al256(maxt * SEG_DIG), b_tok = seg_al256(maxt);
     int32_t r;
     if ((r = ctx_reserve(ctx, ctx->tmp_f, b_off + b_sum + b_ok + b_tab + b_dig + b_tok + 256))) return r;
     uint8_t *base = (uint8_t *)ctx->tmp_f.p;
     uint64_t *d_off = (uint64_t *)base;
+    uint32_t *d_ids = (uint32_t *)(base + seg_al256((m + 1) * 8));
     uint8_t *sums = out_fmt == C25519_FMT_RAW160 ? d_out : base + b_off;
     uint8_t *okbuf = d_ok ? d_ok : base + b_off + b_sum;
     uint4 *tab = (uint4 *)(base + b_off + b_sum + b_ok);
@@ -209,7 +305,9 @@ static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
         HIPCHK(hipMemsetAsync(flags, 0, 8, st));
         HIPCHK(hipEventRecord(ctx->ev0, st));
         HIPCHK(hipMemcpyAsync(d_off, seg_off, (m + 1) * 8, hipMemcpyHostToDevice, st));
-        ctx->kname[0] = "c25519::k_mid_seg_straus (one lane per segment, the doubling chain shared by its terms)";
+        if (!R.wave_ids.empty()) HIPCHK(hipMemcpyAsync(d_ids, R.wave_ids.data(), R.wave_ids.size() * 4, hipMemcpyHostToDevice, st));
+        ctx->kname[0] = R.wave_ids.empty() ? "c25519::k_mid_seg_straus (one lane per segment, the doubling chain shared by its terms)"
+                                           : "c25519::k_mid_seg_wave (one wave per segment, lane l takes terms l, l + 64, ...; the partial sums folded by shuffles)";
         for (const seg_pass &p : passes) {
             const uint64_t t0 = seg_off[p.s0], nt = seg_off[p.s1] - t0, ns = p.s1 - p.s0;
             if (nt) {
@@ -219,9 +317,17 @@ static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
                 else hipLaunchKernelGGL(k_mid_seg_tables<2>, g, b, 0, st, d_scalars, d_points, t0, nt, tab, (uint4 *)dig, tok, flags);
                 HIPCHK(hipGetLastError());
             }
-            hipLaunchKernelGGL(k_mid_seg_straus, dim3(div_up(ns, 256)), dim3(256), 0, st, (const u64 *)d_off, p.s0, ns, t0, nt, (u32)dmax, (const uint4 *)tab,
-                               (const int8_t *)dig, (const uint8_t *)tok, sums, okbuf, flags);
-            HIPCHK(hipGetLastError());
+            if (p.lanes) {                                   // (the wave segments among its lanes are longer than dmax: left alone)
+                hipLaunchKernelGGL(k_mid_seg_straus, dim3(div_up(ns, 256)), dim3(256), 0, st, (const u64 *)d_off, p.s0, ns, t0, nt, (u32)dmax, (const uint4 *)tab,
+                                   (const int8_t *)dig, (const uint8_t *)tok, sums, okbuf, flags);
+                HIPCHK(hipGetLastError());
+            }
+            if (p.w1 > p.w0) {                               // four waves, so four segments, per block; disjoint outputs: back to back on the stream
+                const uint64_t nw = p.w1 - p.w0;
+                hipLaunchKernelGGL(k_mid_seg_wave, dim3(div_up(nw, 4)), dim3(256), 0, st, (const u64 *)d_off, (const u32 *)(d_ids + p.w0), (u32)nw, t0, nt,
+                                   (const uint4 *)tab, (const int8_t *)dig, (const uint8_t *)tok, sums, okbuf, flags);
+                HIPCHK(hipGetLastError());
+            }
         }
         for (size_t k = 0; k < longs.size(); k++) {
             HIPCHK(hipMemcpyAsync(sums + longs[k] * 160, long_sum.data() + 160 * k, 160, hipMemcpyHostToDevice, st));

@@ -230,14 +230,7 @@ __global__ void k_prep_basepoint(u32 *pts, u64 dst) {
 // sum across the 64 lanes of a wave (complete additions; lane 0 ends with the total)
 __device__ __forceinline__ ge_p3 wave_sum(ge_p3 acc) {
 #pragma unroll 1
-    for (int off = 32; off > 0; off >>= 1) {
-        ge_p3 o;
-        for (int i = 0; i < 10; i++) {
-            o.X.v[i] = __shfl_down(acc.X.v[i], off, 64); o.Y.v[i] = __shfl_down(acc.Y.v[i], off, 64);
-            o.Z.v[i] = __shfl_down(acc.Z.v[i], off, 64); o.T.v[i] = __shfl_down(acc.T.v[i], off, 64);
-        }
-        acc = ge_add(acc, o);
-    }
+    for (int off = 32; off > 0; off >>= 1) acc = ge_add(acc, ge_shfl_down(acc, off));
     return acc;
 }
 // one wave per work item: every lane adds its strided share of the segment, then a shuffle tree

@@ -105,7 +105,9 @@ class EdwardsPoint:
     @staticmethod
     def vartime_multiscalar_mul_many(scalar_lists, point_lists, engine=None):
         """[vartime_multiscalar_mul(scalar_lists[k], point_lists[k])] for every k in one call: CompressedEdwardsY bytes, or None where a
-        point of that sum does not decompress.  Unequal lengths inside a pair raise, as in the single form."""
+        point of that sum does not decompress.  Unequal lengths inside a pair raise, as in the single form.  Sums of up to
+        engine.MSM_SEGMENT_WAVE_MAX terms (Bulletproofs-size equations included) all run inside the one call, one GPU lane or one wave each;
+        a longer one costs a single-MSM call of its own (Engine.msm_vartime_segments_plan tells which)."""
         return _msm_many(scalar_lists, point_lists, _e.FMT_EDWARDS_Y, engine)
 
     @staticmethod
@@ -252,7 +254,8 @@ class RistrettoPoint:
 
     @staticmethod
     def vartime_multiscalar_mul_many(scalar_lists, point_lists, engine=None):
-        """[vartime_multiscalar_mul(scalar_lists[k], point_lists[k])] for every k in one call: CompressedRistretto bytes, or None"""
+        """[vartime_multiscalar_mul(scalar_lists[k], point_lists[k])] for every k in one call: CompressedRistretto bytes, or None; routed by
+        length as EdwardsPoint.vartime_multiscalar_mul_many"""
         return _msm_many(scalar_lists, point_lists, _e.FMT_RISTRETTO, engine)
 
     @staticmethod

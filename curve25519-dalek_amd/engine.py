@@ -163,6 +163,7 @@ _SIGS = {
     "c25519_point_sum_segments": (_i32, [_vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_msm_vartime_segments_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_msm_vartime_segments": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
+    "c25519_msm_vartime_segments_plan": (_i32, [_vp, _u64, _vp]),
     "c25519_microbench": (C.c_double, [_vp, C.c_int, C.c_int]),
     "c25519_selftest_field": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _u64, _vp]),
     "c25519_selftest_scalar": (_i32, [_vp, C.c_int, _vp, _vp, _u64, _vp]),
@@ -200,6 +201,7 @@ def load_library():
 _PT = {FMT_EDWARDS_Y: 32, FMT_RISTRETTO: 32, FMT_RAW160: 160}
 PARTIAL_RECORD_BYTES = 9024      # C25519_PARTIAL_RECORD_BYTES
 MSM_SEGMENT_DIRECT_MAX = 64      # C25519_MSM_SEGMENT_DIRECT_MAX: the longest segment msm_vartime_segments runs one per lane
+MSM_SEGMENT_WAVE_MAX = 2048      # C25519_MSM_SEGMENT_WAVE_MAX: the longest segment it runs one per wave; longer ones take the single-MSM path
 MSM_SEGMENT_PASS_TERMS = 1 << 18     # C25519_MSM_SEGMENT_PASS_TERMS: most terms whose tables are resident at once
 
 
@@ -1148,7 +1150,7 @@ class Engine:
     def msm_vartime_segments(self, scalars, points, seg_off, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):
         """many independent vartime MSMs in one call (optional_multiscalar_mul per segment, edwards.rs:1002-1031 / ristretto.rs:984):
         out[s] = sum scalars[i] * points[i] over [seg_off[s], seg_off[s+1]) -> (status OK | NONE, (m, 32|160), ok (m,)); ok[s] = 0 where a
-        point of segment s does not decode"""
+        point of segment s does not decode.  Routed by length: one lane, one wave or a single-MSM call per segment (msm_vartime_segments_plan)"""
         s = _np8(scalars, 32) if len(scalars) else np.zeros((0, 32), np.uint8)
         a = _np8(points, _PT.get(in_fmt, 32)) if len(points) else np.zeros((0, _PT.get(in_fmt, 32)), np.uint8)
         assert s.shape[0] == a.shape[0]
@@ -1160,6 +1162,19 @@ class Engine:
         st = self._chk(self.lib.c25519_msm_vartime_segments(self.ctx, s.ctypes.data, a.ctypes.data, s.shape[0], in_fmt, off.ctypes.data, m, out_fmt,
                                                             out.ctypes.data, ok.ctypes.data), (OK, NONE))
         return st, out, ok
+
+    @staticmethod
+    def msm_vartime_segments_plan(seg_off):
+        """how msm_vartime_segments routes these m + 1 offsets -> (lane segments, wave segments, single-MSM segments, passes, most terms
+        resident in one pass): at most MSM_SEGMENT_DIRECT_MAX terms run one per lane, at most MSM_SEGMENT_WAVE_MAX one per wave, longer ones
+        through the single-MSM path.  Host arithmetic: needs no GPU and no context (a static method); offsets the call would reject raise."""
+        off = np.ascontiguousarray(np.asarray(seg_off, dtype=np.uint64).reshape(-1))
+        assert off.shape[0] >= 1
+        plan = np.zeros(5, np.uint64)
+        st = load_library().c25519_msm_vartime_segments_plan(off.ctypes.data, off.shape[0] - 1, plan.ctypes.data)
+        if st < 0:
+            raise EngineError("HIP error %d: msm_vartime_segments_plan: seg_off must be m + 1 non-decreasing values from 0, below 2^40" % -st)
+        return tuple(int(x) for x in plan)
 
     def scalar_invert_batch(self, scalars):
         """-> (inverses (n,32), product of all inverses (32 bytes)); inputs must be canonical and non-zero."""

@@ -263,20 +263,32 @@ int32_t c25519_fold_partials(c25519_ctx *ctx, const uint8_t *partials160, uint64
  *   - both forms synchronise the context's stream once, at the end, to read the two verdict words.
  *   - every out[s] is byte for byte what c25519_msm_vartime returns for that segment alone (canonical encodings); a RAW160 output is the
  *     same point (equal under ct_eq), not the same limbs.
- * Cost: segments of at most C25519_MSM_SEGMENT_DIRECT_MAX terms run one per GPU lane -- Straus with the doubling chain shared by the
- * terms of the segment (scalar_mul/straus.rs:159-200), radix 16 -- so a wave of 64 consecutive segments costs what its LONGEST one costs:
- * group segments of similar length next to each other.  A longer segment is not what this call is for, but is served: each runs as a
- * c25519_msm_partial_dev of its own (tens of microseconds of latency apiece, one after the other).  The tables of at most
- * C25519_MSM_SEGMENT_PASS_TERMS terms (1344 bytes per term) are resident at a time; more terms run as several passes, cut at segment
- * boundaries.  tools/seg_msm_numbers.py times the call against one c25519_msm_vartime_dev per segment and against c25519_mul_batch_dev +
- * c25519_point_sum_segments_dev. */
-#define C25519_MSM_SEGMENT_DIRECT_MAX 64       /* longest segment the segmented kernels take themselves */
+ * Cost: three routes, chosen by the length of each segment alone (c25519_msm_vartime_segments_plan reports the choice).
+ *   - at most C25519_MSM_SEGMENT_DIRECT_MAX terms: one GPU LANE per segment -- Straus with the doubling chain shared by the terms of the
+ *     segment (scalar_mul/straus.rs:159-200), radix 16 -- so a wave of 64 consecutive segments costs what its LONGEST one costs: group
+ *     segments of similar length next to each other.
+ *   - at most C25519_MSM_SEGMENT_WAVE_MAX terms (Bulletproofs-size verification equations): one WAVE per segment -- lane l runs the same
+ *     loop over terms l, l + 64, ... and the 64 partial sums are folded at the end -- so a segment costs 252 doublings plus ceil(len / 64)
+ *     additions per window in every lane, and thousands of such segments run side by side inside the one call.  (A wave would carry
+ *     64 x 64 terms at the serial depth of the lane route's maximum; from 64 segments per call on it is not slower than the single-MSM
+ *     route up to 2048 terms, which is where the constant stands.  One lone segment is faster through c25519_msm_vartime.)
+ *   - longer: each segment runs as a c25519_msm_partial_dev of its own before the rest is queued (tens of microseconds of latency apiece,
+ *     one after the other).
+ * The tables of at most C25519_MSM_SEGMENT_PASS_TERMS terms (1344 bytes per term) are resident at a time; more terms of the first two
+ * routes run as several passes, cut at segment boundaries.  tools/seg_msm_numbers.py times the call against one c25519_msm_vartime_dev per
+ * segment and against c25519_mul_batch_dev + c25519_point_sum_segments_dev. */
+#define C25519_MSM_SEGMENT_DIRECT_MAX 64       /* longest segment that runs in one lane */
+#define C25519_MSM_SEGMENT_WAVE_MAX 2048       /* longest segment that runs in one wave (measured: DESIGN.md section 3.13) */
 #define C25519_MSM_SEGMENT_PASS_TERMS 262144   /* most terms whose tables are resident at once (2^18: a 352 MB workspace) */
 int32_t c25519_msm_vartime_segments_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt,
                                         const uint64_t *seg_off /* HOST, m + 1 */, uint64_t m, int out_fmt, uint8_t *d_out /* device, m x (32 | 160) */,
                                         uint8_t *d_ok /* device, m bytes, may be NULL */);
 int32_t c25519_msm_vartime_segments(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m,
                                     int out_fmt, uint8_t *out, uint8_t *ok);
+/* how c25519_msm_vartime_segments routes these offsets: plan[0] lane segments, [1] wave segments,
+ * [2] single-MSM segments, [3] passes, [4] most terms resident in one pass.  Same validation and error as the call (n is seg_off[m]).
+ * Host arithmetic: no context, no GPU. */
+int32_t c25519_msm_vartime_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[5]);
 
 /* The same decomposition WITHOUT the partial sum ever visiting the host (what curve25519-dalek_amd/multi.py runs, one
  * process per GPU): c25519_msm_partial_record_dev only ENQUEUES on the context's stream and leaves a fixed-size RECORD in

@@ -11,13 +11,26 @@ printed beside it, and a difference smaller than the spreads is reported as a ti
 compared byte for byte at every timed shape.  Two more rows per constant of the header: segments just below and just above
 C25519_MSM_SEGMENT_DIRECT_MAX (the per-lane chain against one single-MSM call per segment), and 2^20 terms (four passes of
 C25519_MSM_SEGMENT_PASS_TERMS) beside the 2^18 terms of one pass.
-    python tools/seg_msm_numbers.py   (writes profiles/seg_msm_numbers.txt and prints it)"""
+The wave route (more than DIRECT_MAX and at most C25519_MSM_SEGMENT_WAVE_MAX terms, one wave per segment): len 65 .. 4096, each at m = 1, 64
+and 4096 segments (m capped so that m x len <= 2^20), and the pair just below and just above WAVE_MAX; route A beside every row -- what a
+tree without the wave route does for these lengths inside the call, one single-MSM call per segment.  The outputs are compared with route A's
+on the first segments.  A tree whose engine has no MSM_SEGMENT_WAVE_MAX (before the wave route) runs the same rows: run the script on
+both trees on one box in one session, the second time with --append, to see what the route changed.
+    python tools/seg_msm_numbers.py [--root TREE] [--label TEXT] [--append] [--out FILE]
+(writes profiles/seg_msm_numbers.txt of this tree, or FILE, and prints it; --root: import the package from another checkout, built there)"""
+import argparse
 import os
 import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+ap = argparse.ArgumentParser()
+ap.add_argument("--root", default=ROOT, help="the checkout whose package and library are timed")
+ap.add_argument("--label", default="", help="a line that names the tree in the output")
+ap.add_argument("--append", action="store_true", help="append to the output file instead of replacing it")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seg_msm_numbers.txt"))
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.root))
 import numpy as np
 import torch
 
@@ -29,6 +42,8 @@ A_SAMPLE = 2048
 e = pkg.Engine(0)
 ev = pkg.Engine(0, flags=pkg.engine.FLAG_VARTIME_TABLES)
 L, T = pkg.engine.MSM_SEGMENT_DIRECT_MAX, pkg.engine.MSM_SEGMENT_PASS_TERMS
+HAS_WAVE = hasattr(pkg.engine, "MSM_SEGMENT_WAVE_MAX")
+W = pkg.engine.MSM_SEGMENT_WAVE_MAX if HAS_WAVE else 4096     # a tree before the wave route: the same rows, all on its single-MSM route
 g = torch.Generator(device="cuda"); g.manual_seed(11)
 lines = []
 
@@ -64,7 +79,7 @@ def inputs(n):
     return s.contiguous(), pts
 
 
-def route_a(s, pts, off, count):
+def route_a(s, pts, off, count, keep=None):
     lib, ctx = e.lib, e.ctx
     buf = np.zeros(32, np.uint8)
     sp, pp, bp = s.data_ptr(), pts.data_ptr(), buf.ctypes.data
@@ -73,6 +88,8 @@ def route_a(s, pts, off, count):
         a, b = int(off[k]), int(off[k + 1])
         st = lib.c25519_msm_vartime_dev(ctx, sp + 32 * a, pp + 160 * a, b - a, RAW, ED, bp)
         assert st == 0, st
+        if keep is not None:
+            keep.append(bytes(buf))
 
 
 def fmt(t):
@@ -87,7 +104,7 @@ def verdict(new, other):
     return "new x%.1f" % (other[0] / new[0]) if new[0] < other[0] else "NEW LOSES x%.1f" % (new[0] / other[0])
 
 
-def case(name, lengths, with_a=True, with_b=True):
+def case(name, lengths, with_a=True, with_b=True, check_a=0):
     lengths = np.asarray(lengths, dtype=np.int64)
     m, n = len(lengths), int(lengths.sum())
     off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
@@ -102,6 +119,11 @@ def case(name, lengths, with_a=True, with_b=True):
         a = timed(lambda: route_a(s, pts, off, cnt))
         a = tuple(x * m / cnt for x in a)
         row += " | A %s %-16s" % (fmt(a), verdict(new, a))
+        if check_a:                                          # the first check_a sums against the single call's, byte for byte
+            keep = []
+            route_a(s, pts, off, min(m, check_a), keep)
+            got = res["new"][1][:len(keep)].cpu().numpy()
+            assert [bytes(got[k]) for k in range(len(keep))] == keep, "the new call and route A disagree at %s" % name
     if with_b:
         def fb():
             prod, _ = ev.mul_batch_t(s, pts, RAW, RAW)
@@ -113,7 +135,11 @@ def case(name, lengths, with_a=True, with_b=True):
     return new
 
 
-out("segmented vartime MSM, ms per call: median (min .. max) of %d repeats; DIRECT_MAX %d, PASS_TERMS %d; route A scaled from its first %d segments" % (REPS, L, T, A_SAMPLE))
+if args.label:
+    out("==== " + args.label)
+out("multiplier probe (Engine.microbench(0, 4000), best of 100): %.1f Top/s" % (max(e.microbench(0, 4000) for _ in range(100)) / 1e3))
+out("segmented vartime MSM, ms per call: median (min .. max) of %d repeats; DIRECT_MAX %d, WAVE_MAX %s, PASS_TERMS %d; route A scaled from its first %d segments"
+    % (REPS, L, W if HAS_WAVE else "none (no wave route in this tree)", T, A_SAMPLE))
 N = 1 << 18
 for ln in (2, 4, 16, 64):
     case("len %d" % ln, [ln] * (N // ln))
@@ -124,10 +150,18 @@ out("-- around C25519_MSM_SEGMENT_DIRECT_MAX: the per-lane chain against one sin
 for m in (64, 1024):
     case("len %d (direct)" % L, [L] * m, with_b=False)
     case("len %d (long route)" % (L + 1), [L + 1] * m, with_b=False)
+out("-- the wave route: more than DIRECT_MAX and at most WAVE_MAX terms, one wave per segment; m = 1, 64, 4096 capped at m x len <= 2^20")
+for ln in (65, 128, 256, 512, 1024, 2048, 4096):
+    for m in sorted({min(m, (1 << 20) // ln) for m in (1, 64, 4096)}):
+        case("len %d" % ln, [ln] * m, with_b=False, check_a=2)
+out("-- around C25519_MSM_SEGMENT_WAVE_MAX: one wave against one single-MSM call per segment")
+for m in (64, (1 << 20) // (W + 1)):
+    case("len %d (wave)" % W, [W] * m, with_b=False, check_a=2)
+    case("len %d (single-MSM route)" % (W + 1), [W + 1] * m, with_b=False, check_a=2)
 out("-- passes: 2^20 terms are four passes of C25519_MSM_SEGMENT_PASS_TERMS; per term they should cost what one pass costs")
 one = case("len 4, 2^18 terms", [4] * (N // 4), with_a=False, with_b=False)
 four = case("len 4, 2^20 terms", [4] * N, with_a=False, with_b=False)
 out("   ns per term: one pass %.2f, four passes %.2f" % (one[0] * 1e6 / N, four[0] * 1e6 / (4 * N)))
-os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-with open(os.path.join(ROOT, "profiles", "seg_msm_numbers.txt"), "w") as fh:
+os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+with open(args.out, "a" if args.append else "w") as fh:
     fh.write("\n".join(lines) + "\n")
