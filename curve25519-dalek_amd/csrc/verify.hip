@@ -421,6 +421,9 @@ static uint64_t verify_both_max() { static const uint64_t v = (uint64_t)C25519_K
 // (or will be once `ready` has fired) -- decompressed on the second stream while the hashes went to the host and the z_i came back -- with
 // cnt[0] keys and cnt[1] R_i that do not decode
 struct verify_pre { hipEvent_t ready; const uint32_t *cnt; };
+// what a pass over n signatures reserves in the record buffer (tmp_e): B, R_i, A_i and one record of slack.  A caller that fills the buffer BEFORE the pass
+// (verify_pre) reserves exactly this, so the pass's own reservation neither grows nor moves the buffer under the records
+static inline size_t verify_pts_bytes(uint64_t n) { return (size_t)(2 * n + 2) * PTS_BYTES + 256; }
 __global__ void k_add_point_counters(u32 *__restrict__ d_cnt, const u32 *__restrict__ cnt) {
     if (threadIdx.x == 0 && blockIdx.x == 0) { d_cnt[2] += cnt[0]; d_cnt[3] += cnt[1]; }
 }
@@ -431,7 +434,9 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm
     hipStream_t st = ctx->stream;
     const uint64_t m = 2 * n + 1;
     int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_e, (m + 1) * PTS_BYTES + 256))) return r;      // (+ 1: one record of slack)
+    // (pre: the records are in the buffer already, or on their way there -- a reservation that reallocates now would hand the MSM a fresh allocation)
+    if (pre && (ctx != owner || !ctx->tmp_e.p || ctx->tmp_e.cap < verify_pts_bytes(n))) return bad_arg(owner, "verify_batch: internal error (the pre-decompressed records' buffer is smaller than the pass needs)");
+    if ((r = ctx_reserve(ctx, ctx->tmp_e, verify_pts_bytes(n)))) return r;
     // tmp_f: hram (64n) | z16 (16n) | msm scalars (32m) | tree scratch | partial sums
     const unsigned nblk = div_up64(n, 256);
     size_t off = 0;
@@ -655,7 +660,7 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
             // while the hashes go to the host, the transcript runs and the z_i come back (about as long at these sizes); the pass then finds its records ready
             verify_pre pre_pts = {nullptr, nullptr};
             if (!d_pk_points && n <= 4096) {
-                if ((r = ctx_reserve(ctx, ctx->tmp_e, (2 * n + 1) * PTS_BYTES + 256))) return r;
+                if ((r = ctx_reserve(ctx, ctx->tmp_e, verify_pts_bytes(n)))) return r;      // (what the pass will ask for: verify_pass_enqueue refuses a smaller buffer)
                 uint32_t *cnt = (uint32_t *)ctx->d_flag + 44;
                 HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));                 // (the inputs are on the device once the main stream gets here)
                 HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
@@ -855,19 +860,22 @@ static int32_t verify_batch_small_host(c25519_ctx *ctx, const uint8_t *msgs, con
         memcpy(hw, hs + oH + i * 64, 64);
         const bool canon = sc_is_canonical(sw);
         if (!canon) bad_s++;                                       // (the verdict is then ScalarFormat or an earlier one whatever the sum is)
-        // (device z-mode: sign-magnitude, bit 127 = sign.  The general path keeps |z_i| as the scalar and negates the stored R_i so that the R terms stay out of
-        //  the upper windows of a 2^20-term sort; here every term goes through every window anyway: the scalar is z_i mod l)
+        // (device z-mode: sign-magnitude, bit 127 = sign.  As on the general path R_i is multiplied by the INTEGER z_i -- the scalar is |z_i| and the stored R_i is
+        //  negated below (k_apply_sign) -- and s_i, h_i by z_i mod l.  Until the corpus tests the scalar of R_i was z_i mod l = l - |z_i| here: the same for an R_i of
+        //  prime order, but l R_i is not the identity for an R_i with a torsion component, and such a batch got another verdict here than on the general path)
         const bool neg = dev_z && (zw[3] >> 31);
         if (dev_z) zw[3] &= 0x7fffffffu;
         sc52 z = sc_from_words(zw);
-        if (neg) { z = sc_neg(z); sc_to_words(z, zw); }
+        if (neg) z = sc_neg(z);
         const sc52 sc = canon ? sc_from_words(sw) : sc_zero();
         sum = sc_add(sum, sc_mul(z, sc));
         sc_to_words(sc_mul(z, sc_from_wide(hw)), o);
-        memcpy(msc + 32 * (1 + i), zw, 32);                        // R_i: z_i
+        memcpy(msc + 32 * (1 + i), zw, 32);                        // R_i: |z_i|
         memcpy(msc + 32 * (1 + n + i), o, 32);                     // A_i: z_i h_i
     }
     { uint32_t o[8]; sc_to_words(sc_neg(sum), o); memcpy(msc, o, 32); }      // B: -sum z_i s_i   (batch.rs:240)
+    // the sign of z_i onto the stored R_i (behind the decompression on the stream; the z_i are read in place from the staging buffer).  Once: a re-run below finds the records as they are
+    if (dev_z) { hipLaunchKernelGGL(k_apply_sign, dim3(1), dim3(256), 0, ctx->stream, d_pts, (uint64_t)1, (const uint8_t *)(dv + oZ), n); HIPCHK(hipGetLastError()); }
     // ---- the MSM of 2n + 1 terms over the records, published by its last kernel ----
     uint32_t late_cnt[2] = {0, 0};
     r = msm_call_run(ctx, [&](bool allow_direct, msm_call &call) -> int32_t {
