@@ -312,16 +312,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))
 }  // namespace c25519
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------------------------------------------
-// upper end of the path (A/B knob MSM_MID_MAX of the tuning build; 0 = off: the bucket pipeline from 12 288 terms as in round 5)
-// upper ends of the path (A/B knobs of the tuning build; 0 = off: the bucket pipeline from 12 288 terms as in round 5): raw points up to 2^18 terms (200 000 terms 0.47 against 0.54 ms, 2^18 0.57 against 0.58, 400 000
-// 0.78 against 0.71: profiles/r06_ab_mid_upper_end.txt); prepared records -- verify_batch's 2n + 1 terms, whose sort is a third of the bucket pipeline's call -- up to 2^18 + 1
-uint64_t msm_mid_max() { static const uint64_t v = (uint64_t)C25519_KNOB_LL("MSM_MID_MAX", 1 << 18); return v; }
-static uint64_t msm_mid_max_records() { static const uint64_t v = (uint64_t)C25519_KNOB_LL("MSM_MID_MAX_RECORDS", (1 << 18) + 1); return v; }
-bool msm_mid_serves_terms(uint64_t n) { return n > verify_small_max() && n <= msm_mid_max_records(); }      // (verify_batch's prepared records; whatever width the caller is about to choose)
-// (prepared records below msm_small_max() terms: only with a layout that is not the small path's -- verify_batch from verify_small_max() + 1 terms chooses one)
-bool msm_mid_serves(uint64_t n, const msm_geom &g, bool prepared) {
-    return (n > msm_small_max() || (prepared && n > verify_small_max() && g.half > 64)) && n <= (prepared ? msm_mid_max_records() : msm_mid_max()) && g.c >= 8 && g.c <= 16 && g.half >= 64;
-}
+// (the range of the path -- its lower and upper ends for raw points and for prepared records -- is stated with the routes: msm.hip msm_path_of)
 
 // The cap on a bucket lane's list (longer lists go to the waves of the long path).  A lane walks its list as a chain of dependent additions, so the accumulation lasts as
 // long as the longest list below the cap; every list above it costs a wave a ~27 us shuffle tree, which is free beside the bucket lanes as long as there are a few
@@ -365,7 +356,7 @@ int32_t msm_mid_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_
     // (profiles/r06_timeline_mid_verify_2p15_long_cap.txt).  One wave per 256 entries handles such a list in ~30 us.
     msm_geom g = g_in;
     g.long_cap = mid_pick_cap(n, g, (u32)std::max<uint64_t>(48, 3 * (n / (uint64_t)g.half + 1)), src_fmt != 0);
-    if (!msm_mid_serves(n, g, src_fmt != 0) || n >= (1ull << 31)) return bad_arg(ctx, "msm: internal error (mid path outside its range)");
+    if (msm_path_of(n, g, src_fmt != 0, true) != MSM_PATH_MID || n >= (1ull << 31)) return bad_arg(ctx, "msm: internal error (mid path outside its range)");
     if (run && src_fmt == 0) return bad_arg(ctx, "msm: internal error (mid path: a stream override with raw points)");
     hipStream_t st = run && run->stream ? run->stream : ctx->stream;
     const uint64_t dstride = (n + 7) & ~(uint64_t)7;

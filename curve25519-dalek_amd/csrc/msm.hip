@@ -365,7 +365,44 @@ void host_encode(const ge_p3 &R, int out_fmt, uint8_t *out) {
     memcpy(out, w, 32);
 }
 
-// window width for n terms.  c = log2(n) - 4 balances n additions per window against 2 x 2^(c-1) for its bucket reduction: the choice for
+// ---- routes (msm_internal.h msm_route): path, window width and passes of a call are decided HERE and nowhere else.  First the thresholds, all A/B knobs: ----
+// inputs up to this many terms take the single-pass small path (small.hip): 5-bit windows below 1024 terms, 6-bit ones from there (A/B knobs of the tuning
+// build: MSM_SMALL_MAX, and MSM_SMALL_C = the width from 1024 terms).  Rounds 4 and early 5: 4095 terms, 7-bit windows from 2048; round 5 .. late round 6: 12 287
+// terms -- measured against the bucket pipeline's fifteen launches (profiles/r05_ab_small_path_range.txt).  Against the MID path (mid.hip, round 6) the small path
+// holds only up to ~6 000 terms of raw points (profiles/r06_ab_small_mid_boundary.txt, device-resident: 6144 terms 0.164 either way; 8192 0.199 -> 0.177 ms, 10 240
+// 0.237 -> 0.182, 12 287 0.266 -> 0.185 with the 12- / 13-bit windows msm_width gives those sizes) ...
+static uint64_t msm_small_max() { static const uint64_t v = (uint64_t)C25519_KNOB("MSM_SMALL_MAX", 6143); return v; }
+// ... and verify_batch -- prepared (affine) records, half of the scalars 128 bits long: nine of a mid-path layout's windows instead of all of the small path's -- only
+// up to 2047 signatures (same profile, device z-mode: 2048 signatures 0.296 -> 0.273 ms, 3072 0.327 -> 0.284, 4096 0.358 -> 0.291, 6143 0.417 -> 0.309; 1024: 0.252
+// against 0.257).  The term count up to which a batch's 2n + 1-term MSM -- and an MSM over ENCODED points -- stays on the small path
+// (A/B knob VERIFY_SMALL_MAX; never above msm_small_max()):
+static uint64_t verify_small_max() { static const uint64_t v = (uint64_t)C25519_KNOB("VERIFY_SMALL_MAX", 4095); return v < msm_small_max() ? v : msm_small_max(); }
+// upper ends of the mid path (mid.hip; 0 = off: the bucket pipeline from 12 288 terms as in round 5): raw points up to 2^18 terms (200 000 terms 0.47 against 0.54 ms, 2^18 0.57 against 0.58, 400 000
+// 0.78 against 0.71: profiles/r06_ab_mid_upper_end.txt); prepared records -- verify_batch's 2n + 1 terms, whose sort is a third of the bucket pipeline's call -- up to 2^18 + 1
+static uint64_t msm_mid_max() { static const uint64_t v = (uint64_t)C25519_KNOB_LL("MSM_MID_MAX", 1 << 18); return v; }
+static uint64_t msm_mid_max_records() { static const uint64_t v = (uint64_t)C25519_KNOB_LL("MSM_MID_MAX_RECORDS", (1 << 18) + 1); return v; }
+// Pass size: the 128-byte gather records of a pass should stay resident in the 256 MiB MALL while k_accumulate gathers each of
+// them 16 times -- 1.75 M terms = 224 MB (2^21 terms = 268 MB spill: k_accumulate 0.61 - 0.62 ns per term against 0.59 - 0.60, the
+// 2^24-term call 14.32 - 14.54 ms in 8 passes against 14.10 - 14.18 in 10, profiles/r03_ab_pass_size.txt; with the bucket
+// continuation a pass more costs a sort's fixed part, not a reduction).  C25519_MSM_PASS_LOG2 (tests: many small passes) overrides.
+static const uint64_t MSM_PASS = []() -> uint64_t {
+    { const long long v = C25519_KNOB_LL("MSM_PASS_TERMS", 0); if (v >= 65536 && v <= (1ll << 22)) return (uint64_t)v; }      // A/B knob
+    const int v = C25519_KNOB("MSM_PASS_LOG2", 0); if (!v) return (uint64_t)1750000; return 1ull << (v < 16 ? 16 : (v > 22 ? 22 : v)); }();
+static const uint64_t MSM_PASS_MAX = MSM_PASS + MSM_PASS / 2;
+static int pass_lanes() { static const int v = [] { int x = C25519_KNOB("PASS_LANES", 2); return x < 1 ? 1 : (x > 4 ? 4 : x); }(); return v; }   // A/B knob: stream sets (2, 3, 4 measure the same within 3 %: the GPU is saturated)
+
+// the range predicate.  small: within its term range with a layout its LDS tables hold (a forced width may not be: then the bucket pipeline serves); mid: a single pass
+// above that range -- prepared records from verify_small_max() + 1 terms, but only with a layout that is not the small path's (msm_width) -- with windows of 8 .. 16 bits
+int msm_path_of(uint64_t n, const msm_geom &g, bool prepared, bool single) {
+    if (n == 0) return MSM_PATH_EMPTY;
+    if (n <= msm_small_max() && g.half <= 64 && g.nwin <= 64) return MSM_PATH_SMALL;
+    if (single && (n > msm_small_max() || (prepared && n > verify_small_max() && g.half > 64)) && n <= (prepared ? msm_mid_max_records() : msm_mid_max()) && g.c >= 8 && g.c <= 16 && g.half >= 64)
+        return MSM_PATH_MID;
+    return MSM_PATH_PIPELINE;
+}
+bool msm_small_terms(uint64_t n) { return n <= msm_small_max(); }
+
+// every width rule: window width for n terms.  c = log2(n) - 4 balances n additions per window against 2 x 2^(c-1) for its bucket reduction: the choice for
 // THROUGHPUT, from 2^20 terms.  Below that a call is a chain of latencies, and the longest link is k_accumulate's serial walk over a bucket's
 // list (2^(5) = 32 dependent additions at c = log2 n - 4, whatever n): wider windows shorten the lists faster than they lengthen the reduction
 // -- 2^16 terms 0.65 -> 0.45 ms, 2^14 0.55 -> 0.41 (profiles/r04_ab_midrange_windows.txt: +3 bits from 2^13 to 2^16 terms, +2 at 2^12 and 2^17,
@@ -380,30 +417,53 @@ static int pick_window(uint64_t n, int cmax) {
     if (c > cmax) c = cmax;
     return c;
 }
-
-// window layout for n terms (see msm_geom): signed windows share the low 254 - c bits evenly, then an unsigned window of c - 2 bits up to
-// bit 251, then the overflow window, bits 252..255 (a canonical scalar leaves at most the recoding carry there).  (Rounds 1-3: unsigned
-// window of c - 1 bits up to bit 252, overflow window 253..255 -- the same signed windows; bit 252 of a canonical scalar is clear, so that
-// unsigned window used only the lower half of its buckets, cf. msm_slice_params.)
-void msm_layout(uint64_t n, msm_geom &g, int cmax_call, int c_exact) {
+// the width of the ONE layout of a call over n terms of the given kind (msm_terms); single: one pass (the rules of the mid path's first sizes apply only then)
+static int msm_width(uint64_t n, int kind, bool single) {
     static const int cmax_env = std::min(17, std::max(12, C25519_KNOB("MSM_CMAX", 17)));      // A/B knob: 16 = rounds 1-3 (profiles/r04_ab_window_17.txt)
     static const int cforce = C25519_KNOB("MSM_CFORCE", 0);       // A/B knob: this width for every plain layout of the process (0 = choose)
+    // verify_batch: at most 16 bits (the z_i are 128-bit: with 16-bit windows they end on a window boundary; a 17-bit layout leaves a 9-bit stub of 2^20 equal-ish digits)
+    const bool batch = kind == MSM_TERMS_BATCH || kind == MSM_TERMS_BATCH_Z;
+    // prepared records of a single pass, inside the mid path's range from where they leave the small path
+    const bool mid_records = single && n > verify_small_max() && n <= msm_mid_max_records();
+    // (late) ENCODED points -- the decompression's affine records, the 7 M accumulation -- leave the small path earlier than raw ones, like verify_batch's: from
+    // verify_small_max() + 1 = 4096 terms, with 12-bit windows up to msm_small_max() (profiles/r06_ab_small_mid_boundary.txt, CompressedEdwardsY, device-resident: 4096 terms
+    // 0.269 -> 0.236 ms, 6143 0.287 -> 0.244; 3072: 0.243 against 0.235, left alone)
+    if (kind == MSM_TERMS_ENCODED && mid_records && n <= msm_small_max()) return 12;
+    if (kind == MSM_TERMS_BATCH_Z) {
+        // (r6, late) the window width of a mid-size batch: the MSM's rule (pick_window) was tuned on 253-bit scalars; here half of the terms carry 127-bit ones
+        // (nine windows instead of nineteen at 14 bits) and 16-bit windows end exactly on the z_i (no top window of a few bits whose lists are over-long).  Measured
+        // (profiles/r06_ab_verify_window.txt): 2^15 signatures 14 bits 0.411 against the rule's 15 0.417 ms; 2^16: 16 bits 0.476 against 15 bits 0.501; 2^13 / 2^14: the rule (13 / 14).
+        static const int verify_c = C25519_KNOB("VERIFY_C", 0);      // A/B knob of the tuning build: 0 = this rule; 8 .. 16 = that width; -1 = the MSM's rule
+        // (late) ... and 12 bits below 8192 terms, where the mid path takes over from the small one at 2048 signatures (profiles/r06_ab_small_mid_boundary.txt: 3072 signatures 12 bits
+        // 0.284, 13 bits 0.293, 11 bits 0.289 ms)
+        if (verify_c >= 8 && verify_c <= 16 && n > verify_small_max()) return verify_c;
+        if (verify_c == 0 && mid_records) return n < 8192 ? 12 : n < 24576 ? 13 : n < 98304 ? 14 : 16;
+    }
     // (a forced width only where the kernels behind it were built for it: the small path's tables hold windows of 5 .. 7 bits, the chunk-local and
     //  digit-matrix sorts scan at least 64 buckets per slice, i.e. windows of >= 7 bits)
-    const bool force_ok = cforce >= 5 && cforce <= 17 && !cmax_call && (n <= msm_small_max() ? cforce <= 7 : cforce >= 7);
+    if (cforce >= 5 && cforce <= 17 && !batch && (n <= msm_small_max() ? cforce <= 7 : cforce >= 7)) return cforce;
     // the small path (small.hip): 5-bit windows below 1024 terms (pick_window's lower clamp), 6-bit ones above (A/B knob MSM_SMALL_C; rounds 4 and early 5: 7 bits from
     // 2048 terms and the bucket pipeline from 4096 -- profiles/r05_ab_small_path_range.txt: 7-bit tables are 40 KB of LDS per block, four blocks per compute unit).
     // (r6) The choice lives HERE, for plain layouts only: inside pick_window it also narrowed msm_merged_layout's windows (the precomputed-static
     // MSM never takes the small path) from 7 .. 12 bits to 6 for 121 .. 722 static points -- twice the digit-terms, all in 32 buckets.
-    const bool small_c = n >= 1024 && n <= msm_small_max();
-    g.c = c_exact ? c_exact : force_ok ? cforce : small_c ? C25519_KNOB("MSM_SMALL_C", 6) : pick_window(n, cmax_call ? std::min(cmax_call, cmax_env) : cmax_env);
+    if (n >= 1024 && n <= msm_small_max()) return C25519_KNOB("MSM_SMALL_C", 6);
+    int c = pick_window(n, batch ? std::min(16, cmax_env) : cmax_env);
     // (r6) the first sizes of the mid path (mid.hip) want wider windows than the rule, which was tuned on the bucket pipeline in round 4: 13 bits for 8192 .. 16 383 terms
     // (profiles/r06_ab_mid_window.txt: 12 288 terms 0.231 -> 0.213 ms) and 12 bits below (the rule: 10; profiles/r06_ab_small_mid_boundary.txt: 6144 terms 0.229 -> 0.165 ms,
     // 11 bits 0.177, 13 bits 0.175); every other size of the path is at its optimum under the rule
-    if (!c_exact && !force_ok && !small_c && n > msm_small_max() && n < 16384) {
-        if (g.c == 12) g.c = 13;
-        else if (g.c == 10 && n < 8192) g.c = 12;
+    if (n > msm_small_max() && n < 16384) {
+        if (c == 12) c = 13;
+        else if (c == 10 && n < 8192) c = 12;
     }
+    return c;
+}
+
+// window layout of n terms with c-bit windows (see msm_geom): signed windows share the low 254 - c bits evenly, then an unsigned window of c - 2 bits up to
+// bit 251, then the overflow window, bits 252..255 (a canonical scalar leaves at most the recoding carry there).  (Rounds 1-3: unsigned
+// window of c - 1 bits up to bit 252, overflow window 253..255 -- the same signed windows; bit 252 of a canonical scalar is clear, so that
+// unsigned window used only the lower half of its buckets, cf. msm_slice_params.)
+void msm_layout(uint64_t n, int c, msm_geom &g) {
+    g.c = c;
     g.half = 1 << (g.c - 1);
     const int low_bits = 253 - (g.c - 1), nsig = (low_bits + g.c - 1) / g.c, wbase = low_bits / nsig, wrem = low_bits % nsig;
     uint32_t a[9] = {0};
@@ -422,10 +482,71 @@ void msm_layout(uint64_t n, msm_geom &g, int cmax_call, int c_exact) {
     msm_slice_params(g);
     for (int i = 0; i < 8; i++) g.addk[i] = a[i];
 }
+
+// the two constructors; first ONE pass over `terms` terms: width, layout, path
+static void route_single(msm_route &rt, uint64_t terms, int kind, bool prepared, bool solo) {
+    rt.passes = 1; rt.per = rt.layout_terms = terms;
+    msm_layout(terms, msm_width(terms, kind, solo), rt.g);
+    rt.path = msm_path_of(terms, rt.g, prepared, solo);
+}
+msm_route msm_route_points(uint64_t n, int in_fmt, bool fetch, uint64_t pass_terms) {
+    msm_route rt;
+    if (n == 0) return rt;
+    const bool raw = in_fmt == C25519_FMT_RAW160;
+    rt.prep_points = !raw;
+    const uint64_t PT = pass_terms ? pass_terms : MSM_PASS, PTMAX = pass_terms ? pass_terms + pass_terms / 2 : MSM_PASS_MAX;
+    if (n > PTMAX) {                                         // several passes: the bucket pipeline; the layout waits for the number of stream sets (msm_route_lanes)
+        rt.path = MSM_PATH_PIPELINE;
+        rt.passes = (n + PT - 1) / PT; rt.per = (n + rt.passes - 1) / rt.passes;
+        return rt;
+    }
+    route_single(rt, n, raw ? MSM_TERMS_POINTS : MSM_TERMS_ENCODED, !raw, true);
+    // (r5) A small call on raw points: the small path publishes the record itself -- no sticky-word memset and no k_slot_init before it, no copy launch behind it
+    // (small.hip small_direct): 112 -> ~65 us for a 1-term call (profiles/r05_small_call_phases.txt).  A/B knob SMALL_DIRECT = 0: rounds 4's five launches.
+    // (r6) the mid path (mid.hip: four launches on the call's stream) publishes its record the same way.  Encodings never do (the decompression counts what
+    // does not decode into the slot), nor does a small call whose inputs are still on their way up.
+    static const int small_direct_knob = C25519_KNOB("SMALL_DIRECT", 1);
+    rt.publish = small_direct_knob && raw && (rt.path == MSM_PATH_MID || (rt.path == MSM_PATH_SMALL && !fetch));
+    return rt;
+}
+// One layout for every pass: their column sums add up window by window.  It is derived from the terms of a pass -- or, when stream sets
+// get more than one pass each, from at least 2^21: their passes continue each other's bucket sums, ONE reduction serves all of them, and
+// the wider window (17 bits: 15 additions per term instead of 16) costs what a single pass of 2^21 terms pays for it.  The record header
+// carries the number the layout was derived from (records_fold re-derives it from there).
+void msm_route_lanes(msm_route &rt, int lanes) {
+    if (rt.passes <= 1) return;
+    rt.layout_terms = (rt.passes > (uint64_t)lanes && rt.per >= (1ull << 20)) ? std::max<uint64_t>(rt.per, 1ull << 21) : rt.per;
+    // (every pass of such a call takes the bucket pipeline, whose sorts want windows of at least 7 bits: MSM_SMALL_MAX beyond a pass size does not bring them to the small path)
+    msm_layout(rt.layout_terms, std::max(7, msm_width(rt.layout_terms, MSM_TERMS_POINTS, false)), rt.g);
+}
+msm_route msm_route_records(uint64_t terms, int kind, bool solo) {
+    msm_route rt;
+    route_single(rt, terms, kind, true, solo);
+    return rt;
+}
+msm_geom msm_geom_for(uint64_t n) { return msm_route_records(n, MSM_TERMS_POINTS, false).g; }      // "the layout for n terms"
+
+// A host-pointer MSM beyond the small path's term range sends its inputs up pass by pass on the copy stream while the previous pass computes.  Raw points are
+// 192 bytes per term: the link (56 GB/s = 0.29 G terms/s) is slower than the kernels (1.1 G terms/s), so passes are small (2^19 terms) and what remains after
+// the last byte has arrived is one small pass; compressed points (64 bytes per term) are bound by their decompression instead.
+static uint64_t host_pass_terms(uint64_t n, int in_fmt) { return n >= (1ull << 20) ? (in_fmt == C25519_FMT_RAW160 ? (1ull << 19) : (1ull << 20)) : 0; }
+// diagnostics (host only, no GPU and no context needed): the route of a call -- the call itself routes with the same code
+EXPORT int32_t c25519_msm_route(int32_t kind, uint64_t n, int32_t in_fmt, int32_t host_pointers, int64_t route[7]) {
+    if (kind < 0 || kind > 1 || n >= (1ull << 40) || (kind == 0 && (in_fmt < 0 || in_fmt > 2))) return -(int32_t)hipErrorInvalidValue;
+    msm_route rt;
+    if (kind == 1) { if (n) rt = verify_route(n, MSM_TERMS_BATCH_Z, host_pointers && 2 * n + 1 > small_upload_max_terms()); }
+    else {
+        const bool fetch = host_pointers && !msm_small_terms(n);
+        rt = msm_route_points(n, in_fmt, fetch, fetch ? host_pass_terms(n, in_fmt) : 0);
+        msm_route_lanes(rt, (int)std::min<uint64_t>(rt.passes, (uint64_t)pass_lanes()));
+    }
+    const int64_t v[7] = {rt.path, rt.path == MSM_PATH_EMPTY ? 0 : rt.g.c, (int64_t)rt.passes, (int64_t)rt.per, rt.publish, rt.prep_points, (int64_t)rt.layout_terms};
+    for (int i = 0; i < 7; i++) route[i] = v[i];
+    return C25519_OK;
+}
 // diagnostics (host only, no GPU needed): the layout the MSM would use for n terms
 EXPORT int32_t c25519_msm_geometry(uint64_t n, int32_t *c, int32_t *nwin, uint8_t *pos, uint8_t *wid, uint32_t *addk) {
-    msm_geom g;
-    msm_layout(n, g);
+    const msm_geom g = msm_geom_for(n);
     *c = g.c; *nwin = g.nwin;
     for (int k = 0; k < g.nwin; k++) { pos[k] = g.pos[k]; wid[k] = g.wid[k]; }
     for (int i = 0; i < 8; i++) addk[i] = g.addk[i];
@@ -436,9 +557,8 @@ EXPORT int32_t c25519_msm_geometry(uint64_t n, int32_t *c, int32_t *nwin, uint8_
 // stream -- for kernel traces of the sort without an accumulation beside it (tools/sort_only.py)
 EXPORT int32_t c25519_debug_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, uint64_t layout_terms, int32_t reps) {
     HIPCHK(hipSetDevice(ctx->device));
-    if (n <= msm_small_max() || n > (1ull << 22)) return bad_arg(ctx, "debug_sort: n outside the range of a bucket-method pass");
-    msm_geom g;
-    msm_layout(layout_terms ? layout_terms : n, g);
+    if (msm_small_terms(n) || n > (1ull << 22)) return bad_arg(ctx, "debug_sort: n outside the range of a bucket-method pass");
+    const msm_geom g = msm_geom_for(layout_terms ? layout_terms : n);
     for (int i = 0; i < reps; i++) {
         msm_plan pl;
         pl.bad_sticky = nullptr;
@@ -528,7 +648,7 @@ int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_call &call, const msm_plan &p
     if (ring) HIPCHK(hipEventRecord(ring[2], st));
     return C25519_OK;
 }
-// A pass of at most msm_small_max() terms: no sort, no buckets -- small.hip's two launches on the main stream, after whatever the caller
+// A pass on the small path: no sort, no buckets -- small.hip's two launches on the main stream, after whatever the caller
 // put on sort_stream (verify_batch: the batch scalars) and after wait_acc.  src_fmt: 0 raw 160-byte points, 1 affine Niels records.
 static int32_t msm_small_pass(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const msm_geom &g, uint32_t *d_slot,
                               hipEvent_t *ring, hipStream_t sort_stream, hipEvent_t wait_acc) {
@@ -543,11 +663,13 @@ static int32_t msm_small_pass(c25519_ctx *ctx, const msm_call &call, const uint8
     if (ring) { HIPCHK(hipEventRecord(ring[1], st)); HIPCHK(hipEventRecord(ring[2], st)); }
     return C25519_OK;
 }
-int32_t msm_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, const msm_geom &g, uint32_t *d_slot, hipEvent_t *ring,
+int32_t msm_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, const msm_route &rt, uint32_t *d_slot, hipEvent_t *ring,
                     hipStream_t sort_stream, hipEvent_t wait_acc, const mid_run *run) {
     int32_t r;
-    if (n <= msm_small_max() && g.half <= 64) return msm_small_pass(ctx, call, d_scalars, d_pts, 1, n, g, d_slot, ring, sort_stream, wait_acc);   // (g.half: the layout may belong to larger sibling passes)
-    if (call.solo && !wait_acc && msm_mid_serves(n, g, true)) {          // (r6) a single pass of 12 288 .. 2^18 terms over prepared records: the mid path (mid.hip), on the main stream
+    const msm_geom &g = rt.g;
+    if (rt.path == MSM_PATH_SMALL) return msm_small_pass(ctx, call, d_scalars, d_pts, 1, n, g, d_slot, ring, sort_stream, wait_acc);
+    if (rt.path == MSM_PATH_MID) {          // (r6) a single pass over prepared records: the mid path (mid.hip), on the main stream
+        if (!call.solo || wait_acc) return bad_arg(ctx, "msm: internal error (a mid-path route for a pass that is not the call's only one)");
         if (!run && (r = sort_stream_join(ctx, sort_stream))) return r;      // (a pass with a stream override runs ON the stream of its scalars)
         // (no per-kernel events here either -- each is a ~5 us gap between two kernels of a chain that is all critical path: the ring entry of the caller (a verify_batch pass)
         //  is marked so that the accumulation / reduction phases of this call answer -1 instead of reading events of an older one; its own phases stay)
@@ -728,7 +850,7 @@ int32_t records_fold(const uint8_t *records, uint64_t count, ge_p3 &R, uint32_t 
     if (same) {
         if (terms0 == 0) return C25519_OK;                  // empty shards only
         msm_geom g;
-        msm_layout(terms0, g, 0, (int)c0);
+        msm_layout(terms0, (int)c0, g);
         // columns of equal layouts add window by window (host51.h arithmetic), then ONE Horner fold
         std::vector<hp3> hc((size_t)g.nwin);
         for (uint64_t i = 0; i < count; i++) {
@@ -752,7 +874,7 @@ int32_t records_fold(const uint8_t *records, uint64_t count, ge_p3 &R, uint32_t 
         const uint64_t terms = (uint64_t)f[REC_TERMS_LO] | ((uint64_t)f[REC_TERMS_HI] << 32);
         if (terms == 0) continue;
         msm_geom g;
-        msm_layout(terms, g, 0, (int)f[REC_C]);
+        msm_layout(terms, (int)f[REC_C], g);
         memcpy(cols.data(), c, (size_t)g.nwin * 160);        // (records are only 4-byte aligned in general)
         R = ge_add(R, msm_horner(cols.data(), g));
     }
@@ -767,17 +889,16 @@ int32_t msm_core(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, const ui
     constexpr uint64_t CORE_PASS = 1ull << 22;
     for (uint64_t lo = 0; lo < n || lo == 0; lo += CORE_PASS) {
         const uint64_t m = std::min(CORE_PASS, n - lo);
-        msm_geom g;
-        msm_layout(m, g);
+        const msm_route rt = msm_route_records(m, MSM_TERMS_POINTS, true);
         HIPCHK(hipMemsetAsync(dslot(ctx, 0), 0, C25519_SLOT_U32 * 4, ctx->stream));
         if (m) {
             msm_call call;
             call.solo = true;
-            int32_t r = msm_enqueue(ctx, call, d_scalars + lo * 32, m, d_pts + lo * (PTS_BYTES / 4), g, dslot(ctx, 0), nullptr, nullptr);
+            int32_t r = msm_enqueue(ctx, call, d_scalars + lo * 32, m, d_pts + lo * (PTS_BYTES / 4), rt, dslot(ctx, 0), nullptr, nullptr);
             if (r) return r;
             if ((r = slots_collect(ctx, call, 1))) return r;
             if (slot_flags((uint32_t *)hslot(ctx, 0))[0]) return bad_arg(ctx, "msm: a scalar has bit 255 set (Scalar invariant #1 violated)");
-            R = ge_add(R, msm_horner(hslot(ctx, 0), g));
+            R = ge_add(R, msm_horner(hslot(ctx, 0), rt.g));
         }
         if (n == 0) break;
     }
@@ -887,16 +1008,6 @@ int32_t prep_points_on(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n, int
 // caller's context and a peer context (own streams and workspaces on the same GPU): the low-VALU two thirds of a pass
 // (normalise, sort, reduce) overlap the accumulation of its neighbour.  (Round 1 used a host thread per stream set and
 // a stream synchronisation + host fold per pass.)
-// Pass size: the 128-byte gather records of a pass should stay resident in the 256 MiB MALL while k_accumulate gathers each of
-// them 16 times -- 1.75 M terms = 224 MB (2^21 terms = 268 MB spill: k_accumulate 0.61 - 0.62 ns per term against 0.59 - 0.60, the
-// 2^24-term call 14.32 - 14.54 ms in 8 passes against 14.10 - 14.18 in 10, profiles/r03_ab_pass_size.txt; with the bucket
-// continuation a pass more costs a sort's fixed part, not a reduction).  C25519_MSM_PASS_LOG2 (tests: many small passes) overrides.
-static const uint64_t MSM_PASS = []() -> uint64_t {
-    { const long long v = C25519_KNOB_LL("MSM_PASS_TERMS", 0); if (v >= 65536 && v <= (1ll << 22)) return (uint64_t)v; }      // A/B knob
-    const int v = C25519_KNOB("MSM_PASS_LOG2", 0); if (!v) return (uint64_t)1750000; return 1ull << (v < 16 ? 16 : (v > 22 ? 22 : v)); }();
-static const uint64_t MSM_PASS_MAX = MSM_PASS + MSM_PASS / 2;
-static int pass_lanes() { static const int v = [] { int x = C25519_KNOB("PASS_LANES", 2); return x < 1 ? 1 : (x > 4 ? 4 : x); }(); return v; }   // A/B knob: stream sets (2, 3, 4 measure the same within 3 %: the GPU is saturated)
-
 // the peers' streams start after everything already enqueued on the caller's stream (the inputs are complete)
 int32_t passes_begin(c25519_ctx *ctx, uint64_t passes, pass_set &ps) {
     ps.c[0] = ctx; ps.lanes = 1;
@@ -936,11 +1047,12 @@ hipEvent_t *pass_ring(c25519_ctx *owner, c25519_ctx *c, uint8_t kind) {
 // (A third arm -- the launching pass normalising only its own points, the rest on a third stream behind the first two sorts -- was measured in rounds 5 and 6 and
 //  removed: 13.68 against 13.35 - 13.53 ms, with and without streaming accesses; profiles/r05_ab_prep_split.txt, r06_ab_mall.txt.)
 struct pts_ahead { uint32_t *pts; uint64_t n, offset; hipEvent_t done; bool launch; };
-static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const msm_geom &g, uint64_t terms, uint32_t *d_slot,
+static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const msm_route &rt, uint32_t *d_slot,
                                 hipEvent_t wait_acc, const pts_ahead *ahead = nullptr, hipEvent_t wait_in = nullptr,
                                 bool cont = false, bool reduce = true, uint64_t n_carve = 0, uint32_t *d_bad_sticky = nullptr) {
     int32_t r;
     uint32_t *d_pts;
+    const msm_geom &g = rt.g;
     if (wait_in) HIPCHK(hipStreamWaitEvent(ctx->stream, wait_in, 0));      // host-pointer calls: this pass's inputs are still on their way up
     if (!ahead) {
         if ((r = ctx_reserve(ctx, ctx->tmp_e, std::max(n, n_carve) * PTS_BYTES + 256))) return r;
@@ -957,11 +1069,11 @@ static int32_t msm_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm_ca
     // profiles/r04_msm_2p24_sort_ahead_timeline.txt).  profiles/r04_ab_sort_ahead.txt: 13.39 - 13.51 ms against 13.69 - 13.71 on one box, 13.93 - 14.00
     // against 13.93 - 14.11 on another; the whole sort ahead on a second copy of the lists measured the same and is not kept.
     // (a continuing pass exists only in a call with more passes than stream sets: msm_record_enqueue)
-    const bool early = cont && !wait_in && terms > msm_small_max();
+    const bool early = cont && !wait_in;
     const hipEvent_t lists_free = early ? ctx->ev_fork : nullptr;
     if (!early) HIPCHK(hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-    if (!cont) slot_init(d_slot, terms, nullptr, ctx->stream, g.c);            // (a continuing pass adds its counters to the slot of its stream set)
-    if (terms <= msm_small_max() && g.half <= 64 && g.nwin <= 64 && !cont && reduce && !ahead) {      // (g: a forced width may not be the small path's -- then the bucket pipeline serves)
+    if (!cont) slot_init(d_slot, rt.layout_terms, nullptr, ctx->stream, g.c);            // (a continuing pass adds its counters to the slot of its stream set)
+    if (rt.path == MSM_PATH_SMALL) {      // (the only pass of its call -- msm_route_points gives several passes the pipeline, msm_route_lanes clamps their width to >= 7 bits)
         // the small path (small.hip): raw points as they are (projective: no normalisation, no inversion); compressed ones through the
         // decompression into records first
         if (in_fmt == C25519_FMT_RAW160) return msm_small_pass(ctx, call, d_scalars, d_points, 0, n, g, d_slot, ring, nullptr, wait_acc);
@@ -1007,39 +1119,23 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
         HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
         return C25519_OK;
     }
-    const uint64_t PT = pass_terms ? pass_terms : MSM_PASS, PTMAX = pass_terms ? pass_terms + pass_terms / 2 : MSM_PASS_MAX;
-    const uint64_t passes = n <= PTMAX ? 1 : (n + PT - 1) / PT, per = (n + passes - 1) / passes;
+    msm_route rt = msm_route_points(n, in_fmt, fetch != nullptr, pass_terms);
+    const uint64_t passes = rt.passes, per = rt.per;
+    const msm_geom &g = rt.g;
     const size_t psz = point_bytes(in_fmt);
-    msm_geom g;
     pass_set ps;
     int32_t r;
     call.solo = passes == 1;
     uint32_t *sticky = (uint32_t *)ctx->d_flag + 40;      // "a scalar has bit 255 set", ORed over the passes of the call
-    // (r5) A small call on raw points whose caller reads the record on the host right away (allow_direct, d_record = the context's own record): the small
-    // path publishes the record itself -- no sticky-word memset and no k_slot_init before it, no copy launch behind it (small.hip small_direct):
-    // 112 -> ~65 us for a 1-term call (profiles/r05_small_call_phases.txt).  A/B knob SMALL_DIRECT = 0: rounds 4's five launches.
-    static const int small_direct_knob = C25519_KNOB("SMALL_DIRECT", 1);
-    // (r6) the mid path (mid.hip: 12 288 .. 2^18 terms in four launches on this stream) publishes its record the same way
-    bool mid = false;
-    // (a host-pointer call of ONE pass has nothing to overlap its upload with: the inputs go up in one piece and the pass waits for them)
-    // (late) ENCODED points -- the decompression's affine records, the 7 M accumulation -- leave the small path earlier than raw ones, like verify_batch's: from
-    // verify_small_max() + 1 = 4096 terms, with 12-bit windows up to msm_small_max() (profiles/r06_ab_small_mid_boundary.txt, CompressedEdwardsY, device-resident: 4096 terms
-    // 0.269 -> 0.236 ms, 6143 0.287 -> 0.244; 3072: 0.243 against 0.235, left alone)
-    const bool enc_mid = in_fmt != C25519_FMT_RAW160 && n > verify_small_max() && n <= msm_small_max();
-    if (passes == 1 && (n > msm_small_max() || enc_mid)) { msm_layout(n, g, 0, enc_mid ? 12 : 0); mid = msm_mid_serves(n, g, in_fmt != C25519_FMT_RAW160); }
-    if (small_direct_knob && allow_direct && d_record == drec(ctx) && in_fmt == C25519_FMT_RAW160 && ((!fetch && n <= msm_small_max()) || mid)) {
-        msm_geom gs;
-        msm_layout(n, gs);
-        if (mid || (gs.half <= 64 && gs.nwin <= 64)) call.seq = publish_next_seq(ctx);
-    }
+    // the last kernel publishes the record itself when the caller reads it on the host right away (a host-pointer call of ONE pass has nothing to overlap its upload with)
+    if (rt.publish && allow_direct && d_record == drec(ctx)) call.seq = publish_next_seq(ctx);
+    const bool mid = rt.path == MSM_PATH_MID;
     if (call.seq && !mid) {
         // (r6) the directly published small call, lean: its two kernels and the bracket of the call -- no phase ring, no fork to the second stream, no pass bookkeeping
         // (eight event records and a cross-stream wait that a 75 us call spent ~8 us of host time on; c25519_last_call_phase_ms answers -1 for such a call)
-        msm_geom gs;
-        msm_layout(n, gs);
         ctx->last_passes.clear();
         ctx->kname[0] = "c25519::k_small_cols (tables of multiples by repeated addition, one lane per (window, term))";
-        if ((r = msm_small_enqueue(ctx, call, d_scalars, d_points, 0, n, gs, d_record, ctx->stream))) return r;
+        if ((r = msm_small_enqueue(ctx, call, d_scalars, d_points, 0, n, g, d_record, ctx->stream))) return r;
         HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
         return C25519_OK;
     }
@@ -1069,12 +1165,7 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
     //  the ~20 us before the first kernels is launch latency, not the event: profiles/r05_ab_midrange_streams.txt; not kept)
     HIPCHK(hipMemsetAsync(sticky, 0, 4, ctx->stream));
     if ((r = passes_begin(ctx, passes, ps))) return r;
-    // One layout for every pass: their column sums add up window by window.  It is derived from the terms of a pass -- or, when stream sets
-    // get more than one pass each, from at least 2^21: their passes continue each other's bucket sums, ONE reduction serves all of them, and
-    // the wider window (17 bits: 15 additions per term instead of 16) costs what a single pass of 2^21 terms pays for it.  The record header
-    // carries the number the layout was derived from (records_fold re-derives it from there).
-    const uint64_t layout_terms = (passes > (uint64_t)ps.lanes && per >= (1ull << 20)) ? std::max<uint64_t>(per, 1ull << 21) : per;
-    msm_layout(layout_terms, g);
+    msm_route_lanes(rt, ps.lanes);                        // a call of several passes: the one layout of them all
     hipEvent_t prev_acc = nullptr;                         // the accumulation of the previous pass (on the other stream set)
     hipEvent_t prev_acc_last = nullptr;
     // raw points, several passes on two stream sets: pass 1 (the first one on the peer) prepares the records of ALL later
@@ -1097,7 +1188,7 @@ static int32_t msm_record_enqueue(c25519_ctx *ctx, const uint8_t *d_scalars, con
         uint32_t *slot = passes == 1 ? d_record : dslot(ctx, l);         // a single pass writes the record itself
         hipEvent_t in_ev = nullptr;
         if (fetch && (r = (*fetch)(lo, m, &in_ev))) return r;
-        if ((r = msm_pass_enqueue(ctx, c, call, d_scalars + lo * 32, d_points + lo * psz, m, in_fmt, g, layout_terms, slot, prev_acc, (ahead && p >= 1) ? &ah : nullptr, in_ev,
+        if ((r = msm_pass_enqueue(ctx, c, call, d_scalars + lo * 32, d_points + lo * psz, m, in_fmt, rt, slot, prev_acc, (ahead && p >= 1) ? &ah : nullptr, in_ev,
                                   !first, last, per, sticky))) {
             if (ctx->err.empty()) ctx->err = c->err;
             return r;
@@ -1148,8 +1239,7 @@ EXPORT int32_t c25519_fold_partial_records(c25519_ctx *ctx, const uint8_t *recor
 EXPORT int32_t c25519_partial_record_pack(const uint8_t *point160, int32_t status, const uint32_t *counters8, uint8_t *record) {
     if (status != C25519_OK && status != C25519_NONE) return -(int32_t)hipErrorInvalidValue;
     std::vector<uint32_t> rec(C25519_SLOT_U32, 0u);
-    msm_geom g;
-    msm_layout(1, g);                                     // terms = 1: window 0 sits at bit 0, so column 0 IS the point
+    const msm_geom g = msm_geom_for(1);                   // terms = 1: window 0 sits at bit 0, so column 0 IS the point
     const ge_p3 id = ge_identity(), P = host_from_raw160(point160);
     for (int k = 0; k < g.nwin; k++) {
         const ge_p3 &q = k == 0 ? P : id;
@@ -1185,7 +1275,7 @@ EXPORT int32_t c25519_msm_vartime(c25519_ctx *ctx, const uint8_t *scalars, const
     const size_t psz = point_bytes(in_fmt);
     int32_t r;
     ctx->host_us[0] = wall_us();
-    if (n <= msm_small_max()) {
+    if (msm_small_terms(n)) {
         // the reference's own benchmark sizes (1 .. 1024 terms) and everything else small.hip serves: the inputs into the page-locked staging buffer (raw points: read
         // there in place by the kernels; encodings: one staged copy up), the kernels, the record published to the host by the last of them
         const void *src[2] = {scalars, points};
@@ -1216,10 +1306,7 @@ EXPORT int32_t c25519_msm_vartime(c25519_ctx *ctx, const uint8_t *scalars, const
     uint8_t *d_s = (uint8_t *)ctx->tmp_a.p, *d_p = (uint8_t *)ctx->tmp_b.p;
     if ((r = ffi_begin(ctx))) return r;
     ffi_guard guard(ctx);
-    // The inputs go up pass by pass on the copy stream while the previous pass computes.  Raw points are 192 bytes per term:
-    // the link (56 GB/s = 0.29 G terms/s) is slower than the kernels (1.1 G terms/s), so passes are small (2^19 terms)
-    // and what remains after the last byte has arrived is one small pass; compressed points (64 bytes per term) are bound
-    // by their decompression instead.
+    // The inputs go up pass by pass on the copy stream while the previous pass computes (host_pass_terms).
     uint64_t up = 0;
     int slot = 0;
     const msm_fetch fetch = [&](uint64_t lo, uint64_t m, hipEvent_t *ready) -> int32_t {
@@ -1233,7 +1320,7 @@ EXPORT int32_t c25519_msm_vartime(c25519_ctx *ctx, const uint8_t *scalars, const
     };
     ge_p3 R;
     uint32_t flags[8];
-    const uint64_t pass_terms = n >= (1ull << 20) ? (in_fmt == C25519_FMT_RAW160 ? (1ull << 19) : (1ull << 20)) : 0;
+    const uint64_t pass_terms = host_pass_terms(n, in_fmt);
     // (the mid path publishes its record itself; the bucket pipeline ignores the wish.  A re-run finds the inputs on the device: no fetch)
     r = msm_call_run(ctx, [&](bool allow_direct, msm_call &call) {
         return msm_record_enqueue(ctx, d_s, d_p, n, in_fmt, drec(ctx), allow_direct, call, allow_direct ? &fetch : nullptr, allow_direct ? pass_terms : 0);

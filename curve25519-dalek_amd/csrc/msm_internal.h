@@ -47,17 +47,6 @@ static inline int red_nseg(int half) { const int seg = 64 << red_lb_log2(half); 
 // was derived from, [10] passes summed, [11] a magic word
 constexpr int REC_TERMS_LO = 8, REC_TERMS_HI = 9, REC_PASSES = 10, REC_MAGIC = 11, REC_C = 12;      // REC_C: the window width of the layout (a record with terms > 0 and no width is rejected by the fold)
 constexpr u32 REC_MAGIC_VALUE = 0x52503235u;               // "52PR"
-// inputs up to this many terms take the single-pass small path (small.hip): 5-bit windows below 1024 terms, 6-bit ones from there (A/B knobs of the tuning
-// build: MSM_SMALL_MAX, and MSM_SMALL_C = the width from 1024 terms).  Rounds 4 and early 5: 4095 terms, 7-bit windows from 2048; round 5 .. late round 6: 12 287
-// terms -- measured against the bucket pipeline's fifteen launches (profiles/r05_ab_small_path_range.txt).  Against the MID path (mid.hip, round 6) the small path
-// holds only up to ~6 000 terms of raw points (profiles/r06_ab_small_mid_boundary.txt, device-resident: 6144 terms 0.164 either way; 8192 0.199 -> 0.177 ms, 10 240
-// 0.237 -> 0.182, 12 287 0.266 -> 0.185 with the 12- / 13-bit windows msm_layout gives those sizes) ...
-inline uint64_t msm_small_max() { static const uint64_t v = (uint64_t)C25519_KNOB("MSM_SMALL_MAX", 6143); return v; }
-// ... and verify_batch -- prepared (affine) records, half of the scalars 128 bits long: nine of a mid-path layout's windows instead of all of the small path's -- only
-// up to 2047 signatures (same profile, device z-mode: 2048 signatures 0.296 -> 0.273 ms, 3072 0.327 -> 0.284, 4096 0.358 -> 0.291, 6143 0.417 -> 0.309; 1024: 0.252
-// against 0.257).  The term count up to which a batch's 2n + 1-term MSM -- and an MSM over ENCODED points (msm.hip msm_record_enqueue) -- stays on the small path
-// (A/B knob VERIFY_SMALL_MAX; never above msm_small_max()):
-inline uint64_t verify_small_max() { static const uint64_t v = (uint64_t)C25519_KNOB("VERIFY_SMALL_MAX", 4095); return v < msm_small_max() ? v : msm_small_max(); }
 // up to how many terms a host-pointer verify_batch sends its five arrays up through the staged ONE-copy upload (capi.hip ffi_small_upload), whichever path its MSM takes.
 // The general route's per-array pageable copies on the copy stream cost ~70 us more up to 8192 signatures, ~40 at 16 384, nothing from 32 768
 // (profiles/r06_ab_verify_staged_upload.txt; rounds 5 - 6: 12 287 terms, the small path's range)
@@ -77,6 +66,29 @@ struct msm_call {
     const uint32_t *extra = nullptr;       // in, with seq: two device words to publish as the record's counters [2], [3] (verify.hip, small batches)
     hipEvent_t block_on = nullptr;         // out, set by the enqueue functions of a long call: the host blocks on it before it polls for the results (publish_and_wait)
 };
+// ---- which path serves a call: ONE host-only decision (msm.hip "routes").  Everything that branches on the path, the window width or "does the
+//      last kernel publish the record" consumes a route value; the thresholds and the width rules are stated once, in msm.hip msm_path_of / msm_width ----
+enum msm_path { MSM_PATH_EMPTY = 0, MSM_PATH_SMALL = 1, MSM_PATH_MID = 2, MSM_PATH_PIPELINE = 3 };      // small.hip / mid.hip / the bucket pipeline (sort, accumulate, reduce)
+// what the terms are: an MSM's raw points or prepared records; its ENCODED points; verify_batch's 2n + 1 records (at most 16 bits); the same in the device z-mode
+enum msm_terms { MSM_TERMS_POINTS = 0, MSM_TERMS_ENCODED = 1, MSM_TERMS_BATCH = 2, MSM_TERMS_BATCH_Z = 3 };
+struct msm_route {
+    int path = MSM_PATH_EMPTY;
+    uint64_t passes = 0, per = 0;          // passes of the call and terms per pass (verify.hip verify_route: signatures per pass)
+    uint64_t layout_terms = 0;             // the term count the ONE layout of the call is derived from (the record header carries it)
+    c25519::msm_geom g = {};
+    bool prep_points = false;              // encoded points: affine Niels records are made first (the decompression)
+    bool publish = false;                  // the path's last kernel may publish the record itself (the caller adds what only the call knows: allow_direct, whose record)
+};
+// the path of `n` terms under layout g.  prepared: the records exist (a decompression made them); single: ONE pass on the call's own context with nothing to wait for
+int msm_path_of(uint64_t n, const c25519::msm_geom &g, bool prepared, bool single);
+bool msm_small_terms(uint64_t n);          // n is inside the small path's term range, whatever the layout (how a host-pointer MSM sends its inputs up)
+// points as the caller gave them (fetch: still on their way up, pass by pass; pass_terms: 0 = default).  Several passes: the layout comes from msm_route_lanes
+msm_route msm_route_points(uint64_t n, int in_fmt, bool fetch, uint64_t pass_terms);
+void msm_route_lanes(msm_route &rt, int lanes);
+// prepared records (kind: MSM_TERMS_POINTS, _BATCH or _BATCH_Z).  solo: one pass on the call's own context.  msm_geom_for: "the layout for n terms"
+msm_route msm_route_records(uint64_t terms, int kind, bool solo);
+c25519::msm_geom msm_geom_for(uint64_t n);
+msm_route verify_route(uint64_t n, int kind, bool staged);      // verify_batch of n > 0 signatures (verify.hip); sets publish for the device z-mode
 // arming a publication (msm.hip): the context's next non-zero sequence number; then, for the enqueue that publishes under it, the DEVICE's view of the host record
 // slot and of the sequence word and the number to release there (counts the call in C25519_CTR_PUBLISH_DIRECT; the tuning build's loss injection changes the number)
 uint32_t publish_next_seq(c25519_ctx *ctx);
@@ -106,10 +118,10 @@ int32_t msm_matrix_sort_enqueue(c25519_ctx *ctx, const c25519::msm_geom &g, cons
 int32_t msm_enqueue_acc(c25519_ctx *ctx, const msm_call &call, const msm_plan &pl, const uint32_t *d_pts, uint32_t *d_slot, hipEvent_t *ring, hipEvent_t wait_acc, bool cont = false,
                         bool reduce = true, const uint32_t *d_bad_sticky = nullptr);
 struct mid_run;
-// sort + accumulate + reduce of one pass over prepared records; inputs of at most msm_small_max() terms take the small path (run: see msm_mid_enqueue; honoured by the mid path only)
-int32_t msm_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, const c25519::msm_geom &g, uint32_t *d_slot, hipEvent_t *ring,
+// sort + accumulate + reduce of one pass over prepared records, by the path of its route (msm_route_records; run: see msm_mid_enqueue; honoured by the mid path only)
+int32_t msm_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, const msm_route &rt, uint32_t *d_slot, hipEvent_t *ring,
                     hipStream_t sort_stream, hipEvent_t wait_acc = nullptr, const struct mid_run *run = nullptr);
-// the whole MSM of at most msm_small_max() terms in two launches, column sums of the layout g to d_slot (small.hip).  src_fmt: 0 = raw 160-byte points,
+// the whole MSM of a small-path route in two launches, column sums of the layout g to d_slot (small.hip).  src_fmt: 0 = raw 160-byte points,
 // 1 = affine Niels records (128 bytes); flags: the slot's counters (bit 255 of a scalar is ORed into flags[0]).  call.seq != 0: the record is published instead
 int32_t msm_small_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const c25519::msm_geom &g, uint32_t *d_slot,
                           hipStream_t st);
@@ -126,7 +138,7 @@ hipEvent_t *pass_ring(c25519_ctx *owner, c25519_ctx *c, uint8_t kind);
 void launch_merged_table(const uint8_t *in_raw, uint64_t ns, int c, int K, uint8_t *out_raw, hipStream_t st);
 // bucket reduction with four waves per point operation (reduce.hip)
 void launch_bucket_reduce4(const uint32_t *buckets, const c25519::msm_geom &g, int nseg, uint32_t *SW, uint32_t *d_slot, const uint32_t *bad_ws, hipStream_t st);
-// (r6) the mid path (mid.hip): 12 288 .. msm_mid_max() terms in four launches on one stream.  reduce_publish: what the fused bucket reduction (reduce.hip
+// (r6) the mid path (mid.hip): the terms of a mid-path route in four launches on one stream.  reduce_publish: what the fused bucket reduction (reduce.hip
 // k_reduce_b4pub) does once its last window is through -- hdr: write the record header (terms, width; the MSM) or leave the slot's own (verify_batch: k_slot_init made it);
 // on: the columns went to the context's page-locked host slot, release `seq` into the host's sequence word
 // dev_flags (hdr 0 and on): the counters of the DEVICE slot (k_slot_init's header, what the hash and decompression kernels counted) -- copied into the published record
@@ -134,9 +146,6 @@ namespace c25519 { struct reduce_publish { int on; uint32_t *host_flag; uint32_t
 void launch_bucket_reduce_pub(const uint32_t *buckets, const c25519::msm_geom &g, int nseg, uint32_t *SW, uint32_t *out, const uint32_t *blockflags, int nflags, uint32_t *done_cnt,
                               const c25519::reduce_publish &pub, hipStream_t st);
 void launch_order_place(const uint32_t *totals, uint64_t nb, const uint32_t *ord_hist, uint32_t *ord_cursor, uint32_t *perm, const c25519::msm_geom &g, hipStream_t st);
-uint64_t msm_mid_max();
-bool msm_mid_serves_terms(uint64_t n);      // prepared records: is this term count inside the path's range (before a layout exists)
-bool msm_mid_serves(uint64_t n, const c25519::msm_geom &g, bool prepared);      // prepared: the records exist (a decompression made them)
 // run (may be null; prepared records only): the pass runs on run->stream instead of the context's main stream (verify_batch: the stream its scalars were made on -- no
 // hand-over in front of the digits), waits for run->recs_ready (the records, made on the other stream) only in front of the accumulation, and negates there the
 // records sign_first .. sign_first + sign_count - 1 whose sign_z16 entry (16 bytes each, bit 127) is set (verify.hip k_apply_sign: the sign of the device z-mode's z_i);
@@ -152,9 +161,8 @@ const char *launch_accumulate(const uint32_t *pts, const uint32_t *sorted, const
 // the same with long_blocks blocks in front that fold the over-long lists of the mid path (items: mid_item work list of mid.hip; counters[0] = its length)
 const char *launch_accumulate_long(const uint32_t *pts, const uint32_t *sorted, const uint32_t *base, const uint32_t *perm, uint64_t count, uint64_t n, const c25519::msm_geom &g, uint32_t *buckets,
                                    const void *items, const uint32_t *counters, uint32_t *seg_sums, uint32_t *long_done, uint32_t max_items, uint32_t long_blocks, hipStream_t st);
-// cmax (0 = the default, 17): upper limit of the window width -- verify_batch asks for 16 (its z_i are 128-bit: eight 16-bit windows exactly);
-// c_exact (0 = choose): the width itself (records_fold re-derives a record's layout from its header)
-void msm_layout(uint64_t n, c25519::msm_geom &g, int cmax = 0, int c_exact = 0);
+// width in, layout out: the layout of n terms with c-bit windows (the width comes from the call's route; records_fold takes it from the record's header)
+void msm_layout(uint64_t n, int c, c25519::msm_geom &g);
 // sum_i scalars[i] * pts[i] over packed affine Niels points already on the device (enqueue, one read-back, host fold)
 int32_t msm_core(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n, const uint32_t *d_pts, c25519::ge_p3 &R);
 // window width / count of the merged layout for ns static points; sum_i s_i P_i over the table (first n scalars), result to R

@@ -214,7 +214,7 @@ __global__ void __launch_bounds__(TH) k_small_reduce(const u32 *__restrict__ par
 }  // namespace c25519
 
 int32_t msm_small_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_scalars, const void *d_points, int src_fmt, uint64_t n, const msm_geom &g, uint32_t *d_slot, hipStream_t st) {
-    if (n == 0 || n > msm_small_max() || g.half > 64 || g.nwin > SMALL_SLOTS) return bad_arg(ctx, "msm: internal error (small path outside its range)");
+    if (msm_path_of(n, g, src_fmt != 0, false) != MSM_PATH_SMALL || g.nwin > SMALL_SLOTS) return bad_arg(ctx, "msm: internal error (small path outside its range)");
     const int nblocks = (int)((n + SMALL_T - 1) / SMALL_T);
     const size_t lds = (size_t)SMALL_T * g.half * 160;
     // direct publication (call.seq, set by msm_record_enqueue / verify.hip): the record goes to the host's slot, not to d_slot

@@ -409,10 +409,10 @@ static int verify_order(uint64_t n, bool key_bytes) {
     if (n > (1ull << 16)) return 0;
     return k >= 0 ? k : (key_bytes && n <= (1ull << 14)) ? 1 : 0;
 }
-// ... and a single-pass batch whose 2n + 1-term MSM the mid path serves runs it on the hash chain's stream and publishes its record itself
-static bool verify_on_chain(uint64_t n, const msm_geom &g, bool staged) {
+// ... and a single-pass batch whose 2n + 1-term MSM the mid path serves (its route says so) runs it on the hash chain's stream and publishes its record itself
+static bool verify_on_chain(uint64_t n, const msm_route &rt, bool staged) {
     static const int k = C25519_KNOB("MID_ON_CHAIN", 1);     // A/B knob of the tuning build
-    return k != 0 && !staged && n <= (1ull << 16) && msm_mid_serves(2 * n + 1, g, true);
+    return k != 0 && !staged && n <= (1ull << 16) && rt.path == MSM_PATH_MID;
 }
 // keys as BYTES: up to this many signatures A_i and R_i are decompressed by ONE launch of 2n lanes (one latency chain instead of two; rounds 3-5: 4096 -- A/B knob
 // VERIFY_BOTH_MAX of the tuning build; profiles/r06_ab_verify_both.txt)
@@ -429,10 +429,11 @@ __global__ void k_add_point_counters(u32 *__restrict__ d_cnt, const u32 *__restr
 }
 static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm_call &call, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len,
                                    const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points, uint64_t n, uint32_t z_mode,
-                                   const uint8_t *d_hram_pre, const uint8_t *d_z_pre, const uint32_t *d_pre_flags, const msm_geom &g, uint64_t terms, uint32_t *d_slot, hipEvent_t wait_acc,
+                                   const uint8_t *d_hram_pre, const uint8_t *d_z_pre, const uint32_t *d_pre_flags, const msm_route &rt, uint32_t *d_slot, hipEvent_t wait_acc,
                                    const verify_stage *stage = nullptr, const verify_pre *pre = nullptr) {
     hipStream_t st = ctx->stream;
     const uint64_t m = 2 * n + 1;
+    const msm_geom &g = rt.g;
     int32_t r;
     // (pre: the records are in the buffer already, or on their way there -- a reservation that reallocates now would hand the MSM a fresh allocation)
     if (pre && (ctx != owner || !ctx->tmp_e.p || ctx->tmp_e.cap < verify_pts_bytes(n))) return bad_arg(owner, "verify_batch: internal error (the pre-decompressed records' buffer is smaller than the pass needs)");
@@ -451,7 +452,7 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm
     uint32_t *d_cnt = slot_flags(d_slot);             // [2] bad A, [3] bad R, [4] bad s, [5] bad offsets
     hipEvent_t *ring = pass_ring(owner, ctx, 2);
     HIPCHK(hipEventRecord(ring[3], st));
-    slot_init(d_slot, terms, d_pre_flags, st, g.c);
+    slot_init(d_slot, rt.layout_terms, d_pre_flags, st, g.c);
     // Two independent chains: (S) decompress R_i and A_i -- VALU-bound; (A) hash, derive z_i, batch scalars, sort --
     // partly latency-bound (the tree levels).  They run on two streams and join before the accumulation.
     hipStream_t sa = ctx->aux;
@@ -475,7 +476,7 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm
     // A batch whose MSM takes the mid path (mid.hip) runs that MSM on THIS stream, right behind its scalars: the digits and the sort need nothing else; the records
     // (main stream) are waited for once, in front of the accumulation, and the sign of z_i is applied to R_i there (msm_mid_enqueue, mid_run).  Before: k_bsum_finish ->
     // 30 us (event, k_apply_sign on the main stream, event) -> k_mid_front at 2^14 signatures, plus an event record between k_zderive and k_batch_scalars.
-    const bool on_chain = !stage && !d_hram_pre && !d_z_pre && call.solo && !wait_acc && !pre && verify_on_chain(n, g, false);
+    const bool on_chain = !stage && !d_hram_pre && !d_z_pre && call.solo && !wait_acc && !pre && verify_on_chain(n, rt, false);
     if (chain_first) {
         if ((r = zchain_enqueue(ctx, sa, hred, d_sigs, n, t0, t1, z16))) return r;
         if (!on_chain) HIPCHK(hipEventRecord(ctx->ev_z, sa));
@@ -545,11 +546,11 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm
     if (on_chain) {
         HIPCHK(hipEventRecord(ctx->ev_pts, st));                       // the records of B, R_i and A_i
         const mid_run run = {sa, ctx->ev_pts, z16, 1, n};
-        return msm_enqueue(ctx, call, msc, m, d_pts, g, d_slot, ring, sa, wait_acc, &run);
+        return msm_enqueue(ctx, call, msc, m, d_pts, rt, d_slot, ring, sa, wait_acc, &run);
     }
     if (stage && d_pk_points && (r = prep_A())) return r;   // the keys' points come last: only the accumulation needs them
     // the MSM's digit/sort phase continues on the second stream while (S) is still decompressing
-    return msm_enqueue(ctx, call, msc, m, d_pts, g, d_slot, ring, sa, wait_acc);
+    return msm_enqueue(ctx, call, msc, m, d_pts, rt, d_slot, ring, sa, wait_acc);
 }
 // Batches beyond ~1.5 * 2^20 signatures are checked as several independent random linear combinations of about
 // 2^20 signatures each (same reason as MSM_PASS_MAX; in the device z-mode every pass derives its own z_i from its own
@@ -559,6 +560,19 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm
 // batch was cut.
 static const int VERIFY_PASS_LOG2 = [] { int v = C25519_KNOB("VERIFY_PASS_LOG2", 20); return v < 15 ? 15 : (v > 21 ? 21 : v); }();   // A/B knob
 static const uint64_t VERIFY_PASS = 1ull << VERIFY_PASS_LOG2, VERIFY_PASS_MAX = 3ull << (VERIFY_PASS_LOG2 - 1);
+// the route of a batch of n > 0 signatures: its passes (per: signatures) and the ONE layout of their 2 per + 1-term MSMs.  kind: MSM_TERMS_BATCH_Z (device z-mode)
+// or MSM_TERMS_BATCH (the z_i are given); staged: host pointers, the inputs go up pass by pass
+msm_route verify_route(uint64_t n, int kind, bool staged) {
+    const uint64_t passes = n <= VERIFY_PASS_MAX ? 1 : (n + VERIFY_PASS - 1) / VERIFY_PASS, per = (n + passes - 1) / passes;
+    msm_route rt = msm_route_records(2 * per + 1, kind, passes == 1);
+    rt.passes = passes; rt.per = per;
+    // (r6) a single pass through the mid path, inputs on the device: the last reduction block publishes the record -- columns and the slot's counters -- into the
+    // context's page-locked host slot and the host polls the sequence word (msm.hip wait_published; msm_call_run has the small path's recovery: a lost publication
+    // re-runs the pass once through the slot + copy path) instead of a copy-engine launch and a blocking synchronisation behind the last kernel
+    static const int verify_direct_knob = C25519_KNOB("VERIFY_DIRECT", 1);
+    rt.publish = kind == MSM_TERMS_BATCH_Z && verify_direct_knob && verify_on_chain(n, rt, staged);
+    return rt;
+}
 // flags of a folded verify_batch record + its point -> the reference's verdict (precedence: key decoding, then ScalarFormat
 // for ANY non-canonical s, batch.rs:208-211, then Verify, :244-250)
 static int32_t verify_record_verdict(c25519_ctx *ctx, const ge_p3 &R, const uint32_t flags[8]) {
@@ -578,9 +592,9 @@ static int32_t verify_record_enqueue(c25519_ctx *ctx, const uint8_t *d_sigs, con
     if (n >= (1ull << 40)) return bad_arg(ctx, "verify_batch: n too large");
     const uint32_t *d_pre = (const uint32_t *)(d_hram + n * 64);
     if (n == 0) { ctx->last_passes.clear(); slot_init(d_record, 0, d_pre, ctx->stream, 0); HIPCHK(hipGetLastError()); return C25519_OK; }
-    const uint64_t passes = n <= VERIFY_PASS_MAX ? 1 : (n + VERIFY_PASS - 1) / VERIFY_PASS, per = (n + passes - 1) / passes;
-    msm_geom g;
-    msm_layout(2 * per + 1, g, 16);        // (the z_i are 128-bit: with 16-bit windows they end on a window boundary; a 17-bit layout leaves a 9-bit stub of 2^20 equal-ish digits)
+    const msm_route rt = verify_route(n, MSM_TERMS_BATCH, false);
+    const uint64_t passes = rt.passes, per = rt.per;
+    const msm_geom &g = rt.g;
     int32_t r;
     pass_set ps;
     if ((r = passes_begin(ctx, passes, ps))) return r;
@@ -597,7 +611,7 @@ static int32_t verify_record_enqueue(c25519_ctx *ctx, const uint8_t *d_sigs, con
             c25519_ctx *c = ps.c[(p0 + i) % ps.lanes];
             uint32_t *slot = passes == 1 ? d_record : dslot(ctx, i);
             r = verify_pass_enqueue(ctx, c, call, nullptr, nullptr, 0, d_sigs + lo * 64, d_pks + lo * 32, d_pk_points ? d_pk_points + lo * 160 : nullptr, m, C25519_Z_TRANSCRIPT,
-                                    d_hram + lo * 64, d_z16 + lo * 16, (p0 + i == 0) ? d_pre : nullptr, g, 2 * per + 1, slot, prev_acc, nullptr, passes == 1 ? pre : nullptr);
+                                    d_hram + lo * 64, d_z16 + lo * 16, (p0 + i == 0) ? d_pre : nullptr, rt, slot, prev_acc, nullptr, passes == 1 ? pre : nullptr);
             if (r) { if (ctx->err.empty()) ctx->err = c->err; return r; }
             prev_acc = ps.lanes > 1 ? c->ev_acc : nullptr;
         }
@@ -693,25 +707,11 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
     // device z-mode: every pass derives its own z_i from its own tree and is its own random linear combination (summing
     // passes with independent z_i would open a 2^126 birthday attack across passes); all passes run even after a failure so
     // that the precedence does not depend on where the batch was cut
-    const uint64_t passes = n <= VERIFY_PASS_MAX ? 1 : (n + VERIFY_PASS - 1) / VERIFY_PASS, per = (n + passes - 1) / passes;
-    msm_geom g;
-    // (r6, late) the window width of a mid-size batch: the MSM's rule (msm.hip pick_window) was tuned on 253-bit scalars; here half of the terms carry 127-bit ones
-    // (nine windows instead of nineteen at 14 bits) and 16-bit windows end exactly on the z_i (no top window of a few bits whose lists are over-long).  Measured
-    // (profiles/r06_ab_verify_window.txt): 2^15 signatures 14 bits 0.411 against the rule's 15 0.417 ms; 2^16: 16 bits 0.476 against 15 bits 0.501; 2^13 / 2^14: the rule (13 / 14).
-    static const int verify_c = C25519_KNOB("VERIFY_C", 0);      // A/B knob of the tuning build: 0 = this rule; 8 .. 16 = that width; -1 = the MSM's rule
-    const uint64_t vterms = 2 * per + 1;
-    int vc = 0;
-    // (late) ... and 12 bits below 8192 terms, where the mid path takes over from the small one at 2048 signatures (profiles/r06_ab_small_mid_boundary.txt: 3072 signatures 12 bits
-    // 0.284, 13 bits 0.293, 11 bits 0.289 ms)
-    if (verify_c >= 8 && verify_c <= 16 && vterms > verify_small_max()) vc = verify_c;
-    else if (verify_c == 0 && passes == 1 && msm_mid_serves_terms(vterms)) vc = vterms < 8192 ? 12 : vterms < 24576 ? 13 : vterms < 98304 ? 14 : 16;
-    msm_layout(vterms, g, 16, vc);        // (the z_i are 128-bit: with 16-bit windows they end on a window boundary; a 17-bit layout leaves a 9-bit stub of 2^20 equal-ish digits)
+    // (the window widths of a batch and who publishes its record: msm.hip msm_width, msm_route_records)
+    const msm_route rt = verify_route(n, MSM_TERMS_BATCH_Z, fetch != nullptr);
+    const uint64_t passes = rt.passes, per = rt.per;
+    const msm_geom &g = rt.g;
     pass_set ps;
-    // (r6) a single pass through the mid path, inputs on the device: the last reduction block publishes the record -- columns and the slot's counters -- into the
-    // context's page-locked host slot and the host polls the sequence word (msm.hip wait_published; msm_call_run has the small path's recovery: a lost publication
-    // re-runs the pass once through the slot + copy path) instead of a copy-engine launch and a blocking synchronisation behind the last kernel
-    static const int verify_direct_knob = C25519_KNOB("VERIFY_DIRECT", 1);
-    const bool may_publish = passes == 1 && !fetch && verify_direct_knob && verify_on_chain(n, g, false);
     // (only a call of ONE pass publishes, so a loss can only happen in the first -- the only -- group: the re-run below starts the pass list again.  ev0 and
     //  host_us[0..1] are NOT taken again: after a recovery c25519_last_kernel_ms and the host clock span both attempts)
     bool direct = false;                   // did the latest attempt publish its record (host slot C25519_MAX_SLOTS) instead of leaving it in slot 0
@@ -724,14 +724,14 @@ static int32_t verify_batch_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const u
             int32_t q;
             if (p0 == 0 && (q = passes_begin(ctx, passes, ps))) return q;
             call.solo = passes == 1;
-            direct = allow_direct && may_publish && ps.c[0] == ctx;
+            direct = allow_direct && rt.publish && ps.c[0] == ctx;
             if (direct) call.seq = publish_next_seq(ctx);
             for (int i = 0; i < cnt; i++) {
                 const uint64_t lo = (p0 + i) * per, m = std::min(per, n - lo);
                 c25519_ctx *c = ps.c[(p0 + i) % ps.lanes];
                 const verify_stage stage = [&](int what, hipEvent_t *ready) -> int32_t { return (*fetch)(lo, m, what, ready); };
                 q = verify_pass_enqueue(ctx, c, call, d_msgs, d_msg_off + lo, msgs_len, d_sigs + lo * 64, d_pks + lo * 32, d_pk_points ? d_pk_points + lo * 160 : nullptr, m, z_mode,
-                                        nullptr, nullptr, nullptr, g, 2 * per + 1, dslot(ctx, i), prev_acc, fetch ? &stage : nullptr);
+                                        nullptr, nullptr, nullptr, rt, dslot(ctx, i), prev_acc, fetch ? &stage : nullptr);
                 if (q) { if (ctx->err.empty()) ctx->err = c->err; return q; }
                 prev_acc = ps.lanes > 1 ? c->ev_acc : nullptr;
                 if (n >= (1ull << 16) && !direct) call.block_on = c->ev_acc;
@@ -809,8 +809,9 @@ static bool verify_small_host_ok(uint64_t n, uint32_t z_mode, msm_geom &g) {
     static const int host_max = C25519_KNOB("VERIFY_HOST_MAX", 128);      // A/B knob: 0 = the general path at every size (128 = the one-block decompression kernel's limit;
     //                                                                         the host needs 0.7 - 0.85 us per signature, hidden behind that kernel up to ~100: profiles/r05_small_call_phases.txt)
     if (z_mode > 1 || n == 0 || n > (uint64_t)host_max || n > 128) return false;
-    msm_layout(2 * n + 1, g, 16);
-    return g.half <= 64 && g.nwin <= 64;
+    const msm_route rt = msm_route_records(2 * n + 1, MSM_TERMS_BATCH, true);
+    g = rt.g;
+    return rt.path == MSM_PATH_SMALL;
 }
 static int32_t verify_batch_small_host(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_points, uint64_t n,
                                        uint32_t z_mode, const msm_geom &g) {
@@ -830,6 +831,7 @@ static int32_t verify_batch_small_host(c25519_ctx *ctx, const uint8_t *msgs, con
     ctx->last_passes.clear();
     HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
     HIPCHK(launch_prep_small_verify(dv + oK, pk_points ? dv + oP : nullptr, dv + oS, n, d_pts, cnt, ctx->stream));
+    ctx->kname[0] = "c25519::k_small_cols (tables of multiples by repeated addition, one lane per (window, term))";
     ctx->host_us[1] = wall_us();
     // ---- the host's share, beside the decompression ----
     uint32_t bad_s = 0;

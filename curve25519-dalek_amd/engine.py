@@ -173,6 +173,7 @@ _SIGS = {
     "c25519_debug_workspace_read": (_i32, [_vp, C.c_int, _u64, _u64, _vp]),
     "c25519_debug_workspace_zero": (_i32, [_vp]),
     "c25519_msm_geometry": (_i32, [_u64, _vp, _vp, _vp, _vp, _vp]),
+    "c25519_msm_route": (_i32, [_i32, _u64, _i32, _i32, _vp]),
 }
 ABI_SYMBOLS = list(_SIGS)
 
@@ -1175,6 +1176,18 @@ class Engine:
         if st < 0:
             raise EngineError("HIP error %d: msm_vartime_segments_plan: seg_off must be m + 1 non-decreasing values from 0, below 2^40" % -st)
         return tuple(int(x) for x in plan)
+
+    @staticmethod
+    def msm_route(kind, n, in_fmt=FMT_RAW160, host_pointers=False):
+        """which path serves a call (c25519_msm_route) -> dict: kind 0 = msm_vartime over n points of in_fmt, 1 = verify_batch of n signatures (device z-mode).
+        path: "empty" | "small" | "mid" | "pipeline"; c: window width; passes; per: terms (signatures) per pass; publish: the last kernel publishes the
+        record itself; prep_points: records are made first; layout_terms.  Host arithmetic: needs no GPU and no context (a static method)."""
+        r = np.zeros(7, np.int64)
+        st = load_library().c25519_msm_route(kind, n, in_fmt, 1 if host_pointers else 0, r.ctypes.data)
+        if st < 0:
+            raise EngineError("HIP error %d: msm_route: kind must be 0 or 1, in_fmt a point format, n below 2^40" % -st)
+        return {"path": ("empty", "small", "mid", "pipeline")[int(r[0])], "c": int(r[1]), "passes": int(r[2]), "per": int(r[3]), "publish": bool(r[4]),
+                "prep_points": bool(r[5]), "layout_terms": int(r[6])}
 
     def scalar_invert_batch(self, scalars):
         """-> (inverses (n,32), product of all inverses (32 bytes)); inputs must be canonical and non-zero."""

@@ -656,6 +656,15 @@ int32_t c25519_debug_workspace_zero(c25519_ctx *ctx);
  * signed (digit = slice - 2^(wid-1)).  pos / wid need room for 56 entries.  Used by the CPU tests to check that the
  * digits always recompose the scalar. */
 int32_t c25519_msm_geometry(uint64_t n, int32_t *c, int32_t *nwin, uint8_t *pos, uint8_t *wid, uint32_t *addk);
+/* Which path serves a call (host arithmetic: no context, no GPU; the call itself routes with the same code).  kind 0: c25519_msm_vartime[_dev] over n points
+ * of format in_fmt; kind 1: ed25519_verify_batch[_dev] of n signatures in the device z-mode (in_fmt is ignored).  host_pointers: the host-pointer entry
+ * point; for kind 1 it only decides, by 2n + 1 > 32769 terms, whether the arrays go up pass by pass (then nothing is published) -- message lengths are not
+ * looked at, and the host-pointer call's own route for at most 128 signatures (small path, published) is not reported here.  A first attempt on a
+ * context whose peer context exists (two stream sets).
+ * route[0] path: 0 nothing to do (n = 0), 1 small (csrc/small.hip), 2 mid (csrc/mid.hip), 3 the bucket pipeline; [1] window width; [2] passes; [3] terms
+ * (kind 1: signatures) per pass; [4] 1 = the path's last kernel publishes the record to the host itself; [5] 1 = encoded points: records are made first;
+ * [6] the term count the window layout is derived from. */
+int32_t c25519_msm_route(int32_t kind, uint64_t n, int32_t in_fmt, int32_t host_pointers, int64_t route[7]);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ from corpus import NONE, OK, SCALAR_FORMAT, VERIFY
 pytestmark = pytest.mark.gpu
 
 # n signatures = an MSM of 2n + 1 terms.  128 | 129: host small path -> general path; 2047 | 2048: small -> mid MSM (4095 | 4097 terms); 4096 | 4097: limit of the
-# transcript mode's early decompression; 16384 | 16385: verify_order; 65536 | 65537: verify_both_max and verify_on_chain; 131072 | 131073: mid path -> bucket pipeline
+# transcript mode's early decompression; 16384 | 16385: verify_order; 65536 | 65537: verify_both_max and verify_on_chain (the batch route's mid path up to 2^16 signatures); 131072 | 131073: mid path -> bucket pipeline
 SIZES = (128, 129, 2047, 2048, 4096, 4097, 16384, 16385, 65536, 65537, 131072, 131073)
 POOL = 131073
 FULL = list(itertools.product((0, 1), ("bytes", "points"), ("dev", "host")))
