@@ -12,6 +12,7 @@
 #include "devio.h"
 #include "sc_sha.h"
 #include "blake2b.h"
+#include "ztree.h"
 #include "sc28.h"
 #include "kernels.h"
 #include "ctx.h"
@@ -113,8 +114,7 @@ __global__ void __launch_bounds__(256) k_hram_mod_l(const uint8_t *__restrict__ 
 //   level 0: data = (hram_4j mod l) || s_4j || ... || (hram_4j+3 mod l) || s_4j+3 (absent = zero bytes): 2 blocks per 4 signatures, one lane each
 //   level l: data = four children, ONE compression per node (out[j] = node_l(in[4j] || .. || in[4j+3])).  These levels are pure latency
 //            (one dependent compression is ~8 us for a single wave; SHA-512: 16 - 18): five of them run inside one block (k_ztree_block).
-constexpr int ZTREE_MAX_LEVELS = 16;
-struct ztree_ivs { u64 iv[ZTREE_MAX_LEVELS][8]; };       // iv[l]: the BLAKE2b state after TAG(l, ..)
+// (ZTREE_MAX_LEVELS, ztree_ivs -- iv[l]: the BLAKE2b state after TAG(l, ..) -- live in ztree.h: verify_seg.hip builds the same tree per segment)
 __global__ void __launch_bounds__(256) k_ztree_first(const uint8_t *__restrict__ hred, const uint8_t *__restrict__ sigs, u64 n, ztree_ivs ivs, uint8_t *__restrict__ out) {
     C25519_PRIO_CHAIN();
     u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -308,7 +308,7 @@ void launch_apply_sign(uint32_t *pts, uint64_t dst0, const uint8_t *z16, uint64_
 #include "capi_util.h"
 
 // states of the z tree: iv[l] = the BLAKE2b-256 state after the one-block tag of level l (see k_ztree_first)
-static void ztree_make_ivs(uint64_t n, ztree_ivs &ivs) {
+void ztree_make_ivs(uint64_t n, ztree_ivs &ivs) {
     uint64_t count = n;                                  // inputs of level 0: signatures
     for (int l = 0; l < ZTREE_MAX_LEVELS; l++) {
         if (l > 0 && count <= 1) { for (int q = 0; q < 8; q++) ivs.iv[l][q] = 0; continue; }      // (a level the tree does not have: its state is never read)

@@ -577,6 +577,33 @@ def verify_batch(messages, signatures, verifying_keys, engine=None, z_mode=_e.Z_
                           _e.NONE: "PointDecompression"}[st])
 
 
+def verify_batch_segments(batches, engine=None, z_mode=_e.Z_TRANSCRIPT):
+    """verify_batch (batch.rs:146) over MANY independent batches in one GPU call.  batches: a list of (messages, signatures, verifying_keys)
+    triples -> one entry per batch: None for Ok(()) or the SignatureError verify_batch would raise for that batch alone.  A triple of
+    unequal lengths gives ArrayLength without touching the others.  The keys' cached points are used when every key of every batch is a
+    VerifyingKey."""
+    eng = engine or default_engine()
+    names = {_e.SCALAR_FORMAT: "ScalarFormat", _e.VERIFY: "Verify", _e.NONE: "PointDecompression"}
+    out = [None] * len(batches)
+    msgs, sigs, keys, off, where = [], [], [], [0], []
+    for b, (m, s, k) in enumerate(batches):
+        m, s, k = list(m), list(s), list(k)
+        if not (len(m) == len(s) == len(k)):
+            out[b] = SignatureError("ArrayLength")          # batch.rs:152-165
+            continue
+        msgs += m; sigs += s; keys += k
+        off.append(len(msgs)); where.append(b)
+    if not where:
+        return out
+    pk_points = None
+    if keys and all(isinstance(k, VerifyingKey) for k in keys):
+        pk_points = _cat([k.point for k in keys], 160)
+    st = eng.verify_batch_segments(msgs, sigs, [bytes(k) for k in keys], off, z_mode, pk_points=pk_points)
+    for b, c in zip(where, st):
+        out[b] = None if c == _e.OK else SignatureError(names[int(c)])
+    return out
+
+
 def x25519_public_keys(secrets, engine=None):
     """PublicKey::from(&StaticSecret | &EphemeralSecret) (x25519-dalek/src/x25519.rs:105-109, :255-259), batched:
     EdwardsPoint::mul_base_clamped(secret).to_montgomery() through the fixed-base tables, not the ladder."""

@@ -164,6 +164,9 @@ _SIGS = {
     "c25519_msm_vartime_segments_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_msm_vartime_segments": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_msm_vartime_segments_plan": (_i32, [_vp, _u64, _vp]),
+    "ed25519_verify_batch_segments_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp]),
+    "ed25519_verify_batch_segments": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp]),
+    "ed25519_verify_batch_segments_plan": (_i32, [_vp, _u64, _vp]),
     "c25519_microbench": (C.c_double, [_vp, C.c_int, C.c_int]),
     "c25519_selftest_field": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _u64, _vp]),
     "c25519_selftest_scalar": (_i32, [_vp, C.c_int, _vp, _vp, _u64, _vp]),
@@ -204,6 +207,17 @@ PARTIAL_RECORD_BYTES = 9024      # C25519_PARTIAL_RECORD_BYTES
 MSM_SEGMENT_DIRECT_MAX = 64      # C25519_MSM_SEGMENT_DIRECT_MAX: the longest segment msm_vartime_segments runs one per lane
 MSM_SEGMENT_WAVE_MAX = 2048      # C25519_MSM_SEGMENT_WAVE_MAX: the longest segment it runs one per wave; longer ones take the single-MSM path
 MSM_SEGMENT_PASS_TERMS = 1 << 18     # C25519_MSM_SEGMENT_PASS_TERMS: most terms whose tables are resident at once
+VERIFY_SEGMENT_MAX = 1023        # ED25519_VERIFY_SEGMENT_MAX: the longest segment verify_batch_segments runs through the segmented MSM
+
+
+def _seg_off_host(seg_off):
+    """m + 1 segment offsets as a contiguous uint64 array on the host (a sequence, an array or a CPU tensor)"""
+    if hasattr(seg_off, "is_cuda"):
+        assert not seg_off.is_cuda, "seg_off stays on the host"
+        seg_off = seg_off.numpy()
+    off = np.ascontiguousarray(np.asarray(seg_off, dtype=np.uint64).reshape(-1))
+    assert off.shape[0] >= 1
+    return off
 
 
 def _np8(x, width):
@@ -695,6 +709,22 @@ class Engine:
                                                                 out.data_ptr(), ok.data_ptr()), (OK, NONE))
         return st, out, ok
 
+    def verify_batch_segments_t(self, msgs, msg_off, sigs, pks, seg_off, z_mode=Z_TRANSCRIPT, pk_points=None):
+        """many independent verify_batch calls in one: status[s] is what verify_batch_t returns for signatures [seg_off[s], seg_off[s+1]) alone.
+        msgs, msg_off, sigs, pks, pk_points as for verify_batch_t (CUDA tensors); seg_off m + 1 offsets on the HOST -> (m,) uint8 CUDA tensor"""
+        n = self._t(sigs, 64)
+        assert self._t(pks, 32) == n and msg_off.numel() == n + 1
+        if pk_points is not None:
+            assert self._t(pk_points, 160) == n
+        off = _seg_off_host(seg_off)
+        m = off.shape[0] - 1
+        status = self.torch.empty((m,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        self._chk(self.lib.ed25519_verify_batch_segments_dev(self.ctx, msgs.data_ptr(), msg_off.data_ptr(), msgs.numel(), sigs.data_ptr(), pks.data_ptr(),
+                                                             pk_points.data_ptr() if pk_points is not None else None, n, off.ctypes.data, m, z_mode,
+                                                             status.data_ptr()))
+        return status
+
     # -- host-buffer API (numpy in / numpy out) ---------------------------------------------------
     @staticmethod
     def _out(out, n, width):
@@ -848,6 +878,39 @@ class Engine:
         return self._chk(self.lib.ed25519_verify_batch_keys(self.ctx, blob.ctypes.data, off.ctypes.data, s.ctypes.data, p.ctypes.data,
                                                             pp.ctypes.data if pp is not None else None, n, z_mode),
                          (OK, NONE, SCALAR_FORMAT, VERIFY))
+
+    def verify_batch_segments(self, msgs, sigs, pks, seg_off, z_mode=Z_TRANSCRIPT, pk_points=None):
+        """many independent batches in one call.  msgs / sigs / pks: lists over ALL signatures; seg_off: m + 1 offsets into them; pk_points:
+        optional (n, 160) uint8 array of the keys' decompressed points.  -> numpy uint8 status per segment, each what verify_batch returns
+        for that segment alone (0 OK, 1 bad key, 2 ScalarFormat, 3 Verify; an empty segment is 0)."""
+        n = len(msgs)
+        assert len(sigs) == n and len(pks) == n
+        self._check_items(sigs, 64, "signature"); self._check_items(pks, 32, "public key")
+        off = _seg_off_host(seg_off)
+        m = off.shape[0] - 1
+        status = np.zeros((m,), dtype=np.uint8)
+        blob, moff = self._pack(list(msgs))
+        s = _np8(b"".join(sigs), 64) if n else np.zeros((0, 64), np.uint8)
+        p = _np8(b"".join(pks), 32) if n else np.zeros((0, 32), np.uint8)
+        pp = None
+        if pk_points is not None:
+            pp = _np8(pk_points, 160)
+            assert pp.shape[0] == n
+        self._bind_stream()
+        self._chk(self.lib.ed25519_verify_batch_segments(self.ctx, blob.ctypes.data, moff.ctypes.data, s.ctypes.data, p.ctypes.data,
+                                                         pp.ctypes.data if pp is not None else None, n, off.ctypes.data, m, z_mode, status.ctypes.data))
+        return status
+
+    @staticmethod
+    def verify_batch_segments_plan(seg_off):
+        """how verify_batch_segments routes these m + 1 offsets -> (segments on the segmented route, segments run as single batches, passes,
+        most terms in one pass).  Host arithmetic: no engine, no GPU."""
+        off = _seg_off_host(seg_off)
+        plan = np.zeros(4, dtype=np.uint64)
+        st = load_library().ed25519_verify_batch_segments_plan(off.ctypes.data, off.shape[0] - 1, plan.ctypes.data)
+        if st:
+            raise EngineError("HIP error %d: verify_batch_segments_plan: seg_off must be m + 1 non-decreasing values from 0, below 2^40" % -st)
+        return tuple(int(v) for v in plan)
 
     def debug_batch_zs(self, msgs, sigs, pks, z_mode=Z_DEVICE):
         """The z_i of a batch as an (n, 16) uint8 array (diagnostics, see c25519_debug_batch_zs)."""

@@ -348,6 +348,43 @@ int32_t ed25519_verify_batch_keys_dev(c25519_ctx *ctx, const uint8_t *d_msgs, co
 int32_t ed25519_verify_batch_keys(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off,
                                   const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_points, uint64_t n, uint32_t z_mode);
 
+/* MANY independent batches in one call: status[s] is, byte for byte, what ed25519_verify_batch_keys[_dev] returns for the signatures
+ * [seg_off[s], seg_off[s+1]) alone in the same z_mode (batch.rs:146-251, once per segment) -- a block's transactions, a gossip round's
+ * votes, a certificate chain: batches of 4 .. 256 signatures whose verdicts must stay separate; or the halves, quarters, ... of a large
+ * batch that failed, to locate the defect in one call.
+ *   - status[s]: 0 OK; 1 a key of the segment does not decode; 2 a non-canonical s in the segment; 3 an R that does not decode, or a
+ *     non-identity sum.  Precedence 1 over 2 over 3; an empty segment is 0.  A defect in one segment changes no other segment's status.
+ *   - the return value is C25519_OK whenever the statuses were written, whatever they are (as ed25519_verify_each); negative values are
+ *     argument or HIP errors.  m == 0 returns C25519_OK.
+ *   - seg_off is a HOST array in BOTH forms (the lengths are public and the host routes by them), validated as by
+ *     c25519_msm_vartime_segments: m + 1 non-decreasing values from 0 to n, m below 2^32 - 1; anything else returns -(hipErrorInvalidValue)
+ *     before any launch.  msg_off as for ed25519_verify_batch_dev (the _dev form checks it on the device; no byte outside msgs is read).
+ *   - pk_points (n x 160, or NULL): the contract of ed25519_verify_batch_keys.
+ *   - the z_i of a segment are those the single call derives for that segment alone: C25519_Z_TRANSCRIPT -- one Merlin transcript per
+ *     segment over its hram and s, run on the host (one synchronisation in the middle of the call); C25519_Z_DEVICE -- the hash tree over
+ *     the segment, tagged with the segment's own length.  (Verdicts on points with a torsion component depend on the z_i.)
+ * Route, by the length of each segment alone (ed25519_verify_batch_segments_plan reports it): at most ED25519_VERIFY_SEGMENT_MAX signatures
+ * -- the segment is one segment of 2k + 1 terms [B | R_0 .. R_{k-1} | A_0 .. A_{k-1}] of c25519_msm_vartime_segments_dev (its lane route up to
+ * 31 signatures, its wave route beyond); longer -- the segment runs through ed25519_verify_batch_keys_dev on its slice before anything else is
+ * queued.  Segmented-route work is cut into passes of at most C25519_MSM_SEGMENT_PASS_TERMS terms at segment boundaries.  As on the MSM's lane
+ * route, a wave of 64 consecutive short segments costs what its longest one costs: keep segments of similar length together.
+ * Measured (tools/verify_seg_numbers.py, profiles/verify_seg_numbers.txt; 2^16 device-resident signatures, device
+ * z-mode): 1.6 - 6.3 ms per call for segments of 1 .. 1023 signatures, against 15 ms .. 12.9 s for one ed25519_verify_batch_keys_dev per
+ * segment.  Break-even against the per-segment calls: from 16 segments for lengths 1, 4 and 256, from 8 at 64, from 64 at 16, from 32 at
+ * 1023; a handful of batches is faster one call each.  ed25519_verify_each_dev over the same signatures (1.2 ms) is FASTER at every
+ * measured length, x1.3 (64 per segment) to x5.3 (16 and 1023 per segment), and at 2^20 signatures still x1.4 - x1.9: a caller who only
+ * needs to know which signatures are good calls verify_each.  This call is for callers who need verify_batch's own verdict per batch
+ * (the two differ on keys and R with a torsion component).  The transcript z-mode costs 21 - 47 ms per 2^16 signatures: its host sponge. */
+#define ED25519_VERIFY_SEGMENT_MAX 1023   /* 2k+1 <= C25519_MSM_SEGMENT_WAVE_MAX: longest segment on the segmented route */
+int32_t ed25519_verify_batch_segments_dev(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len,
+                                          const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points /* n x 160 or NULL */, uint64_t n,
+                                          const uint64_t *seg_off /* HOST, m + 1 */, uint64_t m, uint32_t z_mode, uint8_t *d_status /* device, m bytes */);
+int32_t ed25519_verify_batch_segments(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *sigs, const uint8_t *pks,
+                                      const uint8_t *pk_points, uint64_t n, const uint64_t *seg_off, uint64_t m, uint32_t z_mode, uint8_t *status);
+/* how the call routes these offsets: plan[0] segments on the segmented route, [1] segments run as single batches, [2] passes, [3] most terms
+ * in one pass.  Same validation and error as the call (n is seg_off[m]).  Host arithmetic: no context, no GPU. */
+int32_t ed25519_verify_batch_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[4]);
+
 /* ---- verify_batch across ranks with the reference's ONE transcript (C25519_Z_TRANSCRIPT; SURVEY.md 8e: "the sequential
  * transcript runs once on the host and the z_i are scattered") -- the building blocks multi.verify_batch_sharded and
  * ed25519_verify_batch_multi are made of:
