@@ -2,6 +2,7 @@
 // signatures [seg_off[s], seg_off[s+1]) alone (batch.rs:146-251, once per segment).  DESIGN.md section 3.14.
 //
 //   ed25519_verify_batch_segments_dev / ed25519_verify_batch_segments / ed25519_verify_batch_segments_plan
+//   ed25519_batch_transcript_zs_segments_dev / ed25519_batch_transcript_zs_segments / ed25519_batch_transcript_zs_segments_plan
 //
 // A segment of k <= ED25519_VERIFY_SEGMENT_MAX signatures becomes one segment of 2k + 1 terms [B | R_0 .. R_{k-1} | A_0 .. A_{k-1}] of the
 // segmented MSM (mid_seg.hip); a longer one runs through ed25519_verify_batch_keys_dev on its slice before anything else is queued.
@@ -9,6 +10,10 @@
 //   k_mid_vseg_ztree     device z-mode, one WAVE per segment, four per block: the BLAKE2b tree of verify.hip (k_ztree_first / k_ztree_block / k_zderive)
 //                        over the segment alone -- <= 256 leaf nodes and <= 4 upper levels through LDS -- tagged with the segment's own length;
 //                        the per-level states come from a table the host builds once per distinct length (ztree_make_ivs)
+//   k_mid_vseg_transcript   transcript z-mode, one LANE per segment of at most ED25519_TRANSCRIPT_SEGMENT_DEVICE_MAX signatures: the segment's Merlin
+//                        transcript (transcript_dev.h: the sponge in registers, the block under assembly in LDS); longer segments keep the host sponge
+//                        (ed25519_batch_transcript_zs, one synchronisation in the middle of the call -- only when there is such a segment).  Also the
+//                        whole of ed25519_batch_transcript_zs_segments[_dev], there at any length
 //   k_mid_vseg_terms     two lanes per signature: the R lane decodes R_i (negated where z_i is negative), writes |z_i| and z_i s_i mod l and
 //                        records "s >= l" / "R does not decode"; the A lane decodes A_i (or loads the cached point) and writes z_i h_i mod l.
 //                        A point that does not decode is replaced by the identity: the MSM only ever sees points
@@ -37,6 +42,7 @@
 #include "ffi.h"
 #include "knobs.h"
 #include "ztree.h"
+#include "transcript_dev.h"
 #include "capi_util.h"
 
 using namespace c25519;
@@ -133,6 +139,24 @@ __global__ void __launch_bounds__(256) k_mid_vseg_ztree(const u64 *__restrict__ 
             }
         }
     }
+}
+
+// Transcript z-mode: LANE j of the launch takes segment s0 + j (cnt of them) and runs its Merlin transcript (transcript_dev.h) over its hram rows and
+// s halves: len x 16 bytes of z16, the reference's z_i of that segment alone (batch.rs:168-222).  An empty segment and one longer than max_len (the
+// host's share) write nothing.  One wave per block: a wave alone on its SIMD runs a permutation in 11.7 us whatever the number of its lanes, and the
+// 64 lanes of a wave beat the same segments spread over more waves at every size measured (one-wave blocks that share a CU land on one SIMD).
+// stage: the lane's block under assembly, 248 bytes of LDS; the sponge itself stays in registers.  `pre`: the sponge after the domain separator, the
+// same for every transcript.  No barrier: a lane without work leaves.
+__global__ void __launch_bounds__(64) k_mid_vseg_transcript(const u64 *__restrict__ seg_off, u64 s0, u64 cnt, u64 max_len, const u64 *__restrict__ hram,
+                                                        const u64 *__restrict__ sigs, u64 *__restrict__ z16, const c25519_trd::prefix pre) {
+    __shared__ u64 stage[64][c25519_trd::STAGE_WORDS];
+    const u32 lane = threadIdx.x & 63u;
+    const u64 idx = (u64)blockIdx.x * 64 + lane;
+    if (idx >= cnt) return;
+    const u64 a = seg_off[s0 + idx], b = seg_off[s0 + idx + 1];
+    if (b <= a || b - a > max_len) return;
+    for (int w = 0; w < c25519_trd::STAGE_WORDS; w++) stage[lane][w] = 0;
+    c25519_trd::transcript_zs(pre, hram + 8 * a, sigs + 8 * a, b - a, z16 + 2 * a, stage[lane]);
 }
 
 // Lanes [0, np): the R lane of signature a0 + t; lanes [np, 2 np): its A lane.  The pass holds segments [s0, s1) = signatures [a0, a0 + np); segment s
@@ -262,6 +286,73 @@ static int32_t vseg_check_off(c25519_ctx *ctx, uint64_t n, const uint64_t *seg_o
     return C25519_OK;
 }
 
+// ---- the transcripts of the segments ----
+// The longest segment whose transcript ed25519_verify_batch_segments runs on the device (longer ones of the segmented route: the host sponge).
+// (tuning build: other boundaries for an A/B run; 0 = every transcript on the host)
+static uint64_t vseg_tr_dev_max() {
+    static const uint64_t v = (uint64_t)std::min<long long>(ED25519_VERIFY_SEGMENT_MAX, std::max<long long>(0, C25519_KNOB("VSEG_TRANSCRIPT_DEV_MAX", ED25519_TRANSCRIPT_SEGMENT_DEVICE_MAX)));
+    return v;
+}
+static const c25519_trd::prefix &vseg_tr_prefix() {
+    static const c25519_trd::prefix p = [] { c25519_trd::prefix q; c25519_trd::make_prefix(q); return q; }();
+    return p;
+}
+// k_mid_vseg_transcript over segments [0, m) of d_off, those of at most max_len signatures
+static hipError_t vseg_launch_transcript(c25519_ctx *ctx, const uint64_t *d_off, uint64_t m, uint64_t max_len, const uint8_t *d_hram, const uint8_t *d_sigs, uint8_t *d_z16) {
+    hipLaunchKernelGGL(k_mid_vseg_transcript, dim3(div_up(m, 64)), dim3(64), 0, ctx->stream, d_off, (u64)0, m, max_len, (const u64 *)d_hram, (const u64 *)d_sigs,
+                       (u64 *)d_z16, vseg_tr_prefix());
+    return hipGetLastError();
+}
+
+EXPORT int32_t ed25519_batch_transcript_zs_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[2]) {
+    if (m >= 0xffffffffull) return vseg_bad(nullptr, "m");   // before seg_off[m] is read for n
+    int32_t r;
+    if ((r = vseg_check_off(nullptr, (m && seg_off) ? seg_off[m] : 0, seg_off, m))) return r;
+    plan[0] = plan[1] = 0;
+    for (uint64_t s = 0; s < m; s++) {
+        const uint64_t len = seg_off[s + 1] - seg_off[s];
+        if (len <= vseg_tr_dev_max()) plan[0]++;
+        else if (len <= (uint64_t)ED25519_VERIFY_SEGMENT_MAX) plan[1]++;
+    }
+    return C25519_OK;
+}
+
+// every segment on the device, whatever its length; enqueue only
+EXPORT int32_t ed25519_batch_transcript_zs_segments_dev(c25519_ctx *ctx, const uint8_t *d_hram, const uint8_t *d_sigs, uint64_t n, const uint64_t *seg_off, uint64_t m,
+                                                        uint8_t *d_z16) {
+    HIPCHK(hipSetDevice(ctx->device));
+    int32_t r;
+    if ((r = vseg_check_off(ctx, n, seg_off, m))) return r;
+    if (m == 0 || n == 0) return C25519_OK;
+    if (((uintptr_t)d_hram | (uintptr_t)d_sigs | (uintptr_t)d_z16) & 7) return bad_arg(ctx, "batch_transcript_zs_segments: device buffers must be 8-byte aligned");
+    if ((r = ctx_reserve(ctx, ctx->tmp_c2, (m + 1) * 8))) return r;
+    uint64_t *d_off = (uint64_t *)ctx->tmp_c2.p;
+    HIPCHK(hipMemcpyAsync(d_off, seg_off, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));   // (pageable memory: the caller's array is free on return)
+    HIPCHK(hipEventRecord(ctx->ev0, ctx->stream));
+    HIPCHK(vseg_launch_transcript(ctx, d_off, m, ~0ull, d_hram, d_sigs, d_z16));
+    HIPCHK(hipEventRecord(ctx->ev1, ctx->stream));
+    return C25519_OK;
+}
+
+EXPORT int32_t ed25519_batch_transcript_zs_segments(c25519_ctx *ctx, const uint8_t *hram, const uint8_t *sigs, uint64_t n, const uint64_t *seg_off, uint64_t m, uint8_t *z16) {
+    HIPCHK(hipSetDevice(ctx->device));
+    int32_t r;
+    if ((r = vseg_check_off(ctx, n, seg_off, m))) return r;
+    if (m == 0 || n == 0) return C25519_OK;
+    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 64)) || (r = ctx_reserve(ctx, ctx->tmp_c, n * 64)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * 16))) return r;
+    ffi_small_begin(ctx);
+    uint8_t *d_h = (uint8_t *)ctx->tmp_a.p, *d_s = (uint8_t *)ctx->tmp_c.p, *d_z = (uint8_t *)ctx->tmp_b.p;
+    hipError_t e = hipMemcpyAsync(d_h, hram, n * 64, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_s, sigs, n * 64, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return c25519_fail(ctx, e, "hipMemcpyAsync(inputs)"); }
+    r = ed25519_batch_transcript_zs_segments_dev(ctx, d_h, d_s, n, seg_off, m, d_z);
+    if (r == C25519_OK && (e = hipMemcpyAsync(z16, d_z, n * 16, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) r = c25519_fail(ctx, e, "hipMemcpyAsync(z16)");
+    e = hipStreamSynchronize(ctx->stream);                  // (also after an error: no queued copy still touches the caller's memory)
+    if (r == C25519_OK && e != hipSuccess) r = c25519_fail(ctx, e, "hipStreamSynchronize");
+    ffi_small_end(ctx, n * 128 + (m + 1) * 8, n * 16);
+    return r;
+}
+
 // ---- routing: the one place that decides which route a segment takes and where the passes are cut ----
 //   len <= ED25519_VERIFY_SEGMENT_MAX   one segment of 2 len + 1 terms of the segmented MSM (empty segments too: 0 * B is the identity)
 //   longer                              a single batch, ed25519_verify_batch_keys_dev on its slice
@@ -340,6 +431,18 @@ static int32_t vseg_run(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *
             }
         if (ivs.empty()) ivs.assign(VSEG_IV_U64, 0);
     }
+    // transcript z-mode: how many segments of the segmented route run their transcript on the device, how many on the host -- by length alone
+    const uint64_t tr_max = vseg_tr_dev_max();
+    // (n_tr_runs: the runs of consecutive rows the host's segments form)
+    constexpr uint64_t VSEG_TR_RUNS = 32;
+    uint64_t n_tr_dev = 0, n_tr_host = 0, n_tr_runs = 0, tr_end = ~0ull;
+    if (!dev_z)
+        for (const vseg_pass &p : R.passes)
+            for (uint64_t s = p.s0; s < p.s1; s++) {
+                const uint64_t len = seg_off[s + 1] - seg_off[s];
+                if (len > tr_max) { n_tr_host++; if (seg_off[s] != tr_end) n_tr_runs++; tr_end = seg_off[s + 1]; }
+                else if (len) n_tr_dev++;
+            }
     // tmp_c2 (the call): hram | its two counters | z16 | seg_off | tree states | statuses (host form)
     // tmp_d (sized by the largest pass): term scalars | term points | sums | z s | flags of R, of A, of the segments
     const size_t c_h = vseg_al256(n * 64), c_fl = 256, c_z = vseg_al256((n + 4) * 16), c_off = vseg_al256((m + 1) * 8), c_slot = vseg_al256(iv_slot.size() * 2),
@@ -368,8 +471,16 @@ static int32_t vseg_run(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *
         if (dev_z) {
             HIPCHK(hipMemcpyAsync(d_slot, iv_slot.data(), iv_slot.size() * 2, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(d_ivs, ivs.data(), ivs.size() * 8, hipMemcpyHostToDevice, st));
-        } else if (n) {
-            // the reference's transcript (batch.rs:168-222), one per segment, on the host: the one mid-call synchronisation of this z-mode
+        } else if (!n_tr_host) {
+            // the reference's transcript (batch.rs:168-222), one per segment: on the device, one lane each, up to vseg_tr_dev_max() signatures.  (The kernel reads
+            // d_sigs as 64-bit words, as k_mid_vseg_ztree does: the header's general contract has device buffers of 64-byte items 16-byte aligned.)
+            if (n_tr_dev) HIPCHK(vseg_launch_transcript(ctx, d_off, m, tr_max, hram, d_sigs, z16));
+        } else {
+            // ... and with longer segments of the segmented route: those on the host -- the one mid-call synchronisation of this z-mode, only when there is
+            // such a segment.  The hashes and the signatures come to the host first; then the kernel is queued and the host sponge runs BESIDE it, and the
+            // host's rows go back in runs of consecutive rows (the kernel writes the others; empty segments own none).  Where short and long segments
+            // alternate so often that there would be more than VSEG_TR_RUNS such copies, the host goes first instead, its rows go up in ONE copy from the
+            // first to the last of them, and the kernel, queued behind that copy, overwrites the rows in between that are its own.
             int32_t q;
             if ((q = ctx_host_stage(ctx, n * 144 + 64))) return q;
             uint8_t *hh = (uint8_t *)ctx->h_stage, *hs = hh + n * 64, *hz = hs + n * 64;
@@ -378,12 +489,27 @@ static int32_t vseg_run(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *
             HIPCHK(hipMemcpyAsync(h_fl, hfl, 8, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             if (h_fl[1]) return bad_arg(ctx, "verify_batch_segments: msg_off is not monotone or runs past msgs_len");
+            const bool beside = n_tr_runs <= VSEG_TR_RUNS;
+            if (n_tr_dev && beside) HIPCHK(vseg_launch_transcript(ctx, d_off, m, tr_max, hram, d_sigs, z16));
+            uint64_t run_a = 0, run_b = 0, first = n, last = 0;
             for (const vseg_pass &p : R.passes)
                 for (uint64_t s = p.s0; s < p.s1; s++) {
                     const uint64_t a = seg_off[s], len = seg_off[s + 1] - a;
-                    if (len) ed25519_batch_transcript_zs(hh + a * 64, hs + a * 64, len, hz + a * 16);
+                    if (len <= tr_max) continue;
+                    ed25519_batch_transcript_zs(hh + a * 64, hs + a * 64, len, hz + a * 16);
+                    first = std::min(first, a); last = a + len;
+                    if (a != run_b) {
+                        if (beside && run_b > run_a) HIPCHK(hipMemcpyAsync(z16 + run_a * 16, hz + run_a * 16, (run_b - run_a) * 16, hipMemcpyHostToDevice, st));
+                        run_a = a;
+                    }
+                    run_b = a + len;
                 }
-            HIPCHK(hipMemcpyAsync(z16, hz, n * 16, hipMemcpyHostToDevice, st));
+            if (beside) {
+                if (run_b > run_a) HIPCHK(hipMemcpyAsync(z16 + run_a * 16, hz + run_a * 16, (run_b - run_a) * 16, hipMemcpyHostToDevice, st));
+            } else {
+                HIPCHK(hipMemcpyAsync(z16 + first * 16, hz + first * 16, (last - first) * 16, hipMemcpyHostToDevice, st));
+                if (n_tr_dev) HIPCHK(vseg_launch_transcript(ctx, d_off, m, tr_max, hram, d_sigs, z16));
+            }
         }
         for (const vseg_pass &p : R.passes) {
             const uint64_t a0 = seg_off[p.s0], np = seg_off[p.s1] - a0, ns = p.s1 - p.s0;

@@ -167,6 +167,9 @@ _SIGS = {
     "ed25519_verify_batch_segments_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp]),
     "ed25519_verify_batch_segments": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp]),
     "ed25519_verify_batch_segments_plan": (_i32, [_vp, _u64, _vp]),
+    "ed25519_batch_transcript_zs_segments_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "ed25519_batch_transcript_zs_segments": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "ed25519_batch_transcript_zs_segments_plan": (_i32, [_vp, _u64, _vp]),
     "c25519_microbench": (C.c_double, [_vp, C.c_int, C.c_int]),
     "c25519_selftest_field": (_i32, [_vp, C.c_int, C.c_int, _vp, _vp, _u64, _vp]),
     "c25519_selftest_scalar": (_i32, [_vp, C.c_int, _vp, _vp, _u64, _vp]),
@@ -208,6 +211,7 @@ MSM_SEGMENT_DIRECT_MAX = 64      # C25519_MSM_SEGMENT_DIRECT_MAX: the longest se
 MSM_SEGMENT_WAVE_MAX = 2048      # C25519_MSM_SEGMENT_WAVE_MAX: the longest segment it runs one per wave; longer ones take the single-MSM path
 MSM_SEGMENT_PASS_TERMS = 1 << 18     # C25519_MSM_SEGMENT_PASS_TERMS: most terms whose tables are resident at once
 VERIFY_SEGMENT_MAX = 1023        # ED25519_VERIFY_SEGMENT_MAX: the longest segment verify_batch_segments runs through the segmented MSM
+TRANSCRIPT_SEGMENT_DEVICE_MAX = 256      # ED25519_TRANSCRIPT_SEGMENT_DEVICE_MAX: the longest segment whose Merlin transcript verify_batch_segments runs on the device
 
 
 def _seg_off_host(seg_off):
@@ -725,6 +729,23 @@ class Engine:
                                                              status.data_ptr()))
         return status
 
+    def batch_transcript_zs_segments_t(self, hram, sigs, seg_off, out=None):
+        """the reference's z_i (batch.rs:168-222) of many independent batches, one Merlin transcript per segment on the GPU: rows [seg_off[s],
+        seg_off[s+1]) are batch_transcript_zs of that segment alone.  hram: n x 64 bytes (the tensor of batch_hram_t with its trailer will do),
+        sigs (n, 64): uint8 CUDA tensors; seg_off m + 1 offsets on the HOST; out: an (n, 16) uint8 CUDA tensor to write into (rows of no segment
+        stay as they are).  -> (n, 16) uint8 CUDA tensor.  Enqueue only; every segment runs on the device whatever its length."""
+        n = self._t(sigs, 64)
+        assert hram.is_cuda and hram.dtype == self.torch.uint8 and hram.is_contiguous() and hram.numel() in (n * 64, n * 64 + 64)
+        assert n == 0 or hram.data_ptr() % 16 == 0, "device buffers must be 16-byte aligned"
+        off = _seg_off_host(seg_off)
+        m = off.shape[0] - 1
+        if out is None:
+            out = self.torch.empty((n, 16), dtype=self.torch.uint8, device=self.device)
+        assert self._t(out, 16) == n
+        self._bind_stream()
+        self._chk(self.lib.ed25519_batch_transcript_zs_segments_dev(self.ctx, hram.data_ptr(), sigs.data_ptr(), n, off.ctypes.data, m, out.data_ptr()))
+        return out
+
     # -- host-buffer API (numpy in / numpy out) ---------------------------------------------------
     @staticmethod
     def _out(out, n, width):
@@ -910,6 +931,30 @@ class Engine:
         st = load_library().ed25519_verify_batch_segments_plan(off.ctypes.data, off.shape[0] - 1, plan.ctypes.data)
         if st:
             raise EngineError("HIP error %d: verify_batch_segments_plan: seg_off must be m + 1 non-decreasing values from 0, below 2^40" % -st)
+        return tuple(int(v) for v in plan)
+
+    def batch_transcript_zs_segments(self, hram, sigs, seg_off, out=None):
+        """batch_transcript_zs of many independent batches on the GPU: hram (n, 64), sigs (n, 64) uint8 arrays or bytes, seg_off m + 1 offsets
+        -> (n, 16) uint8 array (`out`, when given, is written in place: rows of no segment stay as they are)"""
+        h = _np8(hram, 64); g = _np8(sigs, 64); n = h.shape[0]
+        assert g.shape[0] == n
+        off = _seg_off_host(seg_off)
+        z = np.zeros((n, 16), dtype=np.uint8) if out is None else out
+        assert z.dtype == np.uint8 and z.flags["C_CONTIGUOUS"] and z.shape == (n, 16)
+        self._bind_stream()
+        self._chk(self.lib.ed25519_batch_transcript_zs_segments(self.ctx, h.ctypes.data, g.ctypes.data, n, off.ctypes.data, off.shape[0] - 1, z.ctypes.data))
+        return z
+
+    @staticmethod
+    def batch_transcript_zs_segments_plan(seg_off):
+        """how verify_batch_segments routes the transcripts of these m + 1 offsets in Z_TRANSCRIPT -> (segments whose transcript runs on the device:
+        at most TRANSCRIPT_SEGMENT_DEVICE_MAX signatures; segments whose transcript runs on the host: longer, up to VERIFY_SEGMENT_MAX).  Host
+        arithmetic: no engine, no GPU."""
+        off = _seg_off_host(seg_off)
+        plan = np.zeros(2, dtype=np.uint64)
+        st = load_library().ed25519_batch_transcript_zs_segments_plan(off.ctypes.data, off.shape[0] - 1, plan.ctypes.data)
+        if st:
+            raise EngineError("HIP error %d: batch_transcript_zs_segments_plan: seg_off must be m + 1 non-decreasing values from 0, below 2^40" % -st)
         return tuple(int(v) for v in plan)
 
     def debug_batch_zs(self, msgs, sigs, pks, z_mode=Z_DEVICE):

@@ -361,8 +361,10 @@ int32_t ed25519_verify_batch_keys(c25519_ctx *ctx, const uint8_t *msgs, const ui
  *     before any launch.  msg_off as for ed25519_verify_batch_dev (the _dev form checks it on the device; no byte outside msgs is read).
  *   - pk_points (n x 160, or NULL): the contract of ed25519_verify_batch_keys.
  *   - the z_i of a segment are those the single call derives for that segment alone: C25519_Z_TRANSCRIPT -- one Merlin transcript per
- *     segment over its hram and s, run on the host (one synchronisation in the middle of the call); C25519_Z_DEVICE -- the hash tree over
- *     the segment, tagged with the segment's own length.  (Verdicts on points with a torsion component depend on the z_i.)
+ *     segment over its hram and s: on the device, one lane per segment, up to ED25519_TRANSCRIPT_SEGMENT_DEVICE_MAX signatures; on the host
+ *     for longer segments (one synchronisation in the middle of the call, only when there is such a segment:
+ *     ed25519_batch_transcript_zs_segments_plan reports it); C25519_Z_DEVICE -- the hash tree over the segment, tagged with the segment's
+ *     own length.  (Verdicts on points with a torsion component depend on the z_i.)
  * Route, by the length of each segment alone (ed25519_verify_batch_segments_plan reports it): at most ED25519_VERIFY_SEGMENT_MAX signatures
  * -- the segment is one segment of 2k + 1 terms [B | R_0 .. R_{k-1} | A_0 .. A_{k-1}] of c25519_msm_vartime_segments_dev (its lane route up to
  * 31 signatures, its wave route beyond); longer -- the segment runs through ed25519_verify_batch_keys_dev on its slice before anything else is
@@ -374,7 +376,11 @@ int32_t ed25519_verify_batch_keys(c25519_ctx *ctx, const uint8_t *msgs, const ui
  * 1023; a handful of batches is faster one call each.  ed25519_verify_each_dev over the same signatures (1.2 ms) is FASTER at every
  * measured length, x1.3 (64 per segment) to x5.3 (16 and 1023 per segment), and at 2^20 signatures still x1.4 - x1.9: a caller who only
  * needs to know which signatures are good calls verify_each.  This call is for callers who need verify_batch's own verdict per batch
- * (the two differ on keys and R with a torsion component).  The transcript z-mode costs 21 - 47 ms per 2^16 signatures: its host sponge. */
+ * (the two differ on keys and R with a torsion component).  The transcript z-mode costs 1.9 / 2.5 / 6.4 / 2.8 / 7.5 / 25.0 ms per 2^16
+ * signatures in segments of 1 / 4 / 16 / 64 / 256 / 1023 (device transcripts up to 256 signatures, the host sponge at 1023; 21 - 47 ms
+ * before the transcripts moved to the device).  A call with FEW segments of 64 .. 256 signatures is slower in this z-mode than with the
+ * host sponge it had before -- one segment of 64: 1.2 -> 2.75 ms, one of 256: 2.2 -> 8.1 ms; level from about 64 segments, faster from
+ * 256 -- because a lane's chain costs 20 us per signature however few lanes run: see ed25519_batch_transcript_zs_segments below. */
 #define ED25519_VERIFY_SEGMENT_MAX 1023   /* 2k+1 <= C25519_MSM_SEGMENT_WAVE_MAX: longest segment on the segmented route */
 int32_t ed25519_verify_batch_segments_dev(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *d_msg_off, uint64_t msgs_len,
                                           const uint8_t *d_sigs, const uint8_t *d_pks, const uint8_t *d_pk_points /* n x 160 or NULL */, uint64_t n,
@@ -384,6 +390,36 @@ int32_t ed25519_verify_batch_segments(c25519_ctx *ctx, const uint8_t *msgs, cons
 /* how the call routes these offsets: plan[0] segments on the segmented route, [1] segments run as single batches, [2] passes, [3] most terms
  * in one pass.  Same validation and error as the call (n is seg_off[m]).  Host arithmetic: no context, no GPU. */
 int32_t ed25519_verify_batch_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[4]);
+
+/* The Merlin transcripts of MANY independent batches (batch.rs:168-222 over batch/transcript.rs, once per segment) on the GPU: z16 rows
+ * [seg_off[s], seg_off[s+1]) are, byte for byte, what ed25519_batch_transcript_zs returns for the hram and sigs rows of that segment alone.
+ * One transcript per LANE: STROBE-128/1600 and Keccak-f[1600] with the sponge in registers (csrc/transcript_dev.h).  A transcript is
+ * sequential -- 1.73 permutations per signature, one chain -- so the call's time is that of its LONGEST segment, 20 - 23 us per
+ * signature (11.7 us per permutation: a wave alone on its SIMD), however many segments there are up to 65536, one wave each per 64; the
+ * host function needs 0.29 us per signature, one segment after the other.  THE COST OF A LONG SEGMENT: 1023 signatures hold the call
+ * for 21 - 24 ms, 4096 for 96 ms, while the host function is done with them in 0.3 / 1.3 ms: the device pays off through the NUMBER of
+ * segments, never through the length of one.
+ *   - the _dev form only enqueues on the context's stream and does not synchronise: ed25519_batch_hram_dev -> this ->
+ *     ed25519_verify_batch_record_dev never visits the host.  It runs EVERY segment on the device whatever its length.  d_hram, d_sigs and
+ *     d_z16 are 8-byte aligned; the host form uploads, runs, downloads and synchronises.
+ *   - seg_off is a HOST array in both forms, validated exactly as by ed25519_verify_batch_segments: the same -(hipErrorInvalidValue), before
+ *     any launch; it is free on return.  m == 0 returns C25519_OK; an empty segment writes nothing.
+ *   - ed25519_batch_transcript_zs_segments_plan (host arithmetic, no context): how ed25519_verify_batch_segments routes the transcripts of
+ *     these offsets in C25519_Z_TRANSCRIPT -- plan[0] segments of at most ED25519_TRANSCRIPT_SEGMENT_DEVICE_MAX signatures: on the device;
+ *     plan[1] longer ones up to ED25519_VERIFY_SEGMENT_MAX: the host sponge.  Still longer segments are single batches and counted in neither.
+ * Measured (tools/verify_seg_numbers.py --transcript-arms, the last section of profiles/verify_seg_numbers.txt, DESIGN.md section 3.14;
+ * 2^16 device-resident signatures in segments of 1 / 4 / 16 / 64 / 256 / 1023): the kernel alone 0.046 / 0.10 / 0.34 / 1.30 / 5.13 / 20.7 ms
+ * against 276 / 82 / 35 / 23 / 19.8 / 19.0 ms of the host function over the same segments.  Inside ed25519_verify_batch_segments_dev
+ * (transcript z-mode, cached key points; the arms alternate in one process, spread 0.1 - 0.4 ms): 1.85 / 2.46 / 6.44 / 2.83 / 7.54 / 26.6 ms
+ * with every transcript on the device against 47.3 / 27.6 / 27.0 / 21.0 / 21.6 / 24.9 ms with every one on the host (the parent's code: the same
+ * within the spread) -- the device wins by x25.6 .. x2.9 up to 256 signatures and loses by x1.07 at 1023, hence the constant.  Break-even
+ * against the host path, m segments of one length: from m = 64 at 4 signatures, from 256 at 64 (a tie at 64) and from 256 at 256 (x1.04
+ * slower at 64); below that the host path is faster by up to x2.2 (64) / x3.8 (256), 1.4 / 6 ms per call.  Routing stays by length alone. */
+#define ED25519_TRANSCRIPT_SEGMENT_DEVICE_MAX 256   /* the largest measured length at which the device transcript beats the host's by more than the spread */
+int32_t ed25519_batch_transcript_zs_segments_dev(c25519_ctx *ctx, const uint8_t *d_hram /* n x 64 */, const uint8_t *d_sigs /* n x 64 */, uint64_t n,
+                                                 const uint64_t *seg_off /* HOST, m + 1 */, uint64_t m, uint8_t *d_z16 /* n x 16 */);
+int32_t ed25519_batch_transcript_zs_segments(c25519_ctx *ctx, const uint8_t *hram, const uint8_t *sigs, uint64_t n, const uint64_t *seg_off, uint64_t m, uint8_t *z16);
+int32_t ed25519_batch_transcript_zs_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[2]);
 
 /* ---- verify_batch across ranks with the reference's ONE transcript (C25519_Z_TRANSCRIPT; SURVEY.md 8e: "the sequential
  * transcript runs once on the host and the z_i are scattered") -- the building blocks multi.verify_batch_sharded and
