@@ -21,13 +21,12 @@
 #include "kernels.h"
 #include "ctx.h"
 #include "msm_internal.h"
+#include "precomp.h"
 #include "ffi.h"
 #include "capi_util.h"
 #include <stdexcept>
 
 using namespace c25519;
-
-struct c25519_precomp { uint32_t *d_table; uint64_t n; c25519::msm_merged m; };
 
 namespace c25519 {
 
@@ -175,6 +174,7 @@ EXPORT void c25519_precomp_destroy(c25519_ctx *ctx, c25519_precomp *p) {
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     hipFree(p->d_table);
+    if (p->d_rows) hipFree(p->d_rows);                   // the rows call's comb table (mid_rows.hip)
     delete p;
 }
 EXPORT uint64_t c25519_precomp_len(const c25519_precomp *p) { return p ? p->n : 0; }

@@ -13,6 +13,9 @@ error behaviour), batched, on top of Engine.  Reference entry points mirrored:
   VerifyingKey::verify_prehashed[_strict] / SigningKey::sign_prehashed   verifying.rs:284 / :424, signing.rs:312   (Ed25519ph: verify_each_prehashed, sign_batch_prehashed)
   EdwardsPoint::multiscalar_mul               curve25519-dalek/src/edwards.rs:966-1000
   VartimeEdwardsPrecomputation                curve25519-dalek/src/edwards.rs:1037-1076
+  VartimeRistrettoPrecomputation              curve25519-dalek/src/ristretto.rs:1004
+  Vartime{Edwards,Ristretto}Precomputation::vartime_multiscalar_mul, many rows of scalars over one precomputation in one call
+                                              traits.rs:304-419   (vartime_multiscalar_mul_many)
   RistrettoPoint::double_and_compress_batch   curve25519-dalek/src/ristretto.rs:564
   Scalar::invert_batch                        curve25519-dalek/src/scalar.rs:802
   EdwardsBasepointTable::create / mul_base    curve25519-dalek/src/edwards.rs:1131-1141 / :1192-1209   (any basepoint)
@@ -671,9 +674,11 @@ def multiscalar_mul(scalars, points, engine=None):
 class VartimeEdwardsPrecomputation:
     """edwards.rs:1037-1076 (VartimePrecomputedMultiscalarMul, traits.rs:304-419); points as CompressedEdwardsY."""
 
+    _fmt = _e.FMT_EDWARDS_Y
+
     def __init__(self, static_points, engine=None):
         self.eng = engine or default_engine()
-        self.h = self.eng.precomp_create(_cat(static_points, 32), _e.FMT_EDWARDS_Y)
+        self.h = self.eng.precomp_create(_cat(static_points, 32), self._fmt)
 
     def __len__(self):
         return self.eng.precomp_len(self.h)
@@ -685,13 +690,31 @@ class VartimeEdwardsPrecomputation:
         if len(dynamic_scalars) != len(dynamic_points):
             raise AssertionError("dynamic scalars and points must have equal length")   # precomputed_straus.rs:87
         st, out = self.eng.precomp_msm_vartime(self.h, _cat(static_scalars, 32), _cat(dynamic_scalars, 32), _cat(dynamic_points, 32),
-                                               _e.FMT_EDWARDS_Y, _e.FMT_EDWARDS_Y)
+                                               self._fmt, self._fmt)
         return None if st == _e.NONE else out
 
     def vartime_multiscalar_mul(self, static_scalars):
         return self.vartime_mixed_multiscalar_mul(static_scalars, [], [])
 
+    def vartime_multiscalar_mul_many(self, rows):
+        """[vartime_multiscalar_mul(row)] for every row in ONE call: rows is a list of scalar lists of one length w <= len(self) -> a list of
+        32-byte encodings.  The first call builds the handle's comb table (64 KB per static point, Engine.precomp_rows_table_bytes); handles
+        of more than engine.PRECOMP_ROWS_MAX_POINTS points are refused (call vartime_multiscalar_mul row by row)."""
+        rows = [list(r) for r in rows]
+        w = len(rows[0]) if rows else 0
+        if any(len(r) != w for r in rows):
+            raise AssertionError("vartime_multiscalar_mul_many: every row must have the same number of scalars")
+        s = _cat([x for r in rows for x in r], 32).reshape(len(rows), w, 32)
+        out = self.eng.precomp_msm_vartime_rows(self.h, s, _e.PRECOMP_ROWS_AUTO, self._fmt)
+        return [out[i].tobytes() for i in range(out.shape[0])]
+
     def close(self):
         if self.h:
             self.eng.precomp_destroy(self.h)
             self.h = None
+
+
+class VartimeRistrettoPrecomputation(VartimeEdwardsPrecomputation):
+    """ristretto.rs:1004 (VartimePrecomputedMultiscalarMul for RistrettoPoint): the same precomputation over CompressedRistretto static and
+    dynamic points, results as CompressedRistretto."""
+    _fmt = _e.FMT_RISTRETTO

@@ -127,6 +127,10 @@ _SIGS = {
     "c25519_precomp_destroy": (None, [_vp, _vp]),
     "c25519_precomp_len": (_u64, [_vp]),
     "c25519_precomp_msm_vartime": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
+    "c25519_precomp_msm_vartime_rows_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, _i32, C.c_int, _vp]),
+    "c25519_precomp_msm_vartime_rows": (_i32, [_vp, _vp, _vp, _u64, _u64, _i32, C.c_int, _vp]),
+    "c25519_precomp_msm_vartime_rows_plan": (_i32, [_u64, _u64, _vp]),
+    "c25519_precomp_rows_table_bytes": (_u64, [_vp]),
     "c25519_msm_consttime": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "c25519_double_and_compress_batch_dev": (_i32, [_vp, _vp, _u64, _vp]),
     "c25519_double_and_compress_batch": (_i32, [_vp, _vp, _u64, _vp]),
@@ -212,6 +216,10 @@ MSM_SEGMENT_WAVE_MAX = 2048      # C25519_MSM_SEGMENT_WAVE_MAX: the longest segm
 MSM_SEGMENT_PASS_TERMS = 1 << 18     # C25519_MSM_SEGMENT_PASS_TERMS: most terms whose tables are resident at once
 VERIFY_SEGMENT_MAX = 1023        # ED25519_VERIFY_SEGMENT_MAX: the longest segment verify_batch_segments runs through the segmented MSM
 TRANSCRIPT_SEGMENT_DEVICE_MAX = 256      # ED25519_TRANSCRIPT_SEGMENT_DEVICE_MAX: the longest segment whose Merlin transcript verify_batch_segments runs on the device
+PRECOMP_ROWS_MAX_POINTS = 4096   # C25519_PRECOMP_ROWS_MAX_POINTS: the largest handle precomp_msm_vartime_rows serves (64 KB of comb table per point)
+PRECOMP_ROWS_AUTO, PRECOMP_ROWS_LANE, PRECOMP_ROWS_WAVE = 0, 1, 2      # C25519_PRECOMP_ROWS_*: its route argument (one lane / one wave per row)
+PRECOMP_ROWS_LANE_WIDTH = 16     # C25519_PRECOMP_ROWS_LANE_WIDTH: AUTO takes the lane route only for rows narrower than this ...
+PRECOMP_ROWS_LANE_MIN_ROWS = 32768       # C25519_PRECOMP_ROWS_LANE_MIN_ROWS: ... and only from this many rows
 
 
 def _seg_off_host(seg_off):
@@ -713,6 +721,18 @@ class Engine:
                                                                 out.data_ptr(), ok.data_ptr()), (OK, NONE))
         return st, out, ok
 
+    def precomp_msm_vartime_rows_t(self, h, scalars, route=PRECOMP_ROWS_AUTO, out_fmt=FMT_EDWARDS_Y):
+        """many multiscalar muls over one precomputation: out[r] = sum_j scalars[r][j] * S_j over the first w static points of the handle h.
+        scalars (m, w, 32) uint8 CUDA tensor -> (m, 32|160) CUDA tensor, on torch's current stream (the call synchronises it once)"""
+        assert scalars.dim() == 3 and scalars.shape[2] == 32, "scalars must have shape (m, w, 32)"
+        m, w = int(scalars.shape[0]), int(scalars.shape[1])
+        if scalars.numel():
+            self._t(scalars, 32)
+        out = self.torch.empty((m, _PT.get(out_fmt, 32)), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        self._chk(self.lib.c25519_precomp_msm_vartime_rows_dev(self.ctx, h, scalars.data_ptr(), m, w, route, out_fmt, out.data_ptr()))
+        return out
+
     def verify_batch_segments_t(self, msgs, msg_off, sigs, pks, seg_off, z_mode=Z_TRANSCRIPT, pk_points=None):
         """many independent verify_batch calls in one: status[s] is what verify_batch_t returns for signatures [seg_off[s], seg_off[s+1]) alone.
         msgs, msg_off, sigs, pks, pk_points as for verify_batch_t (CUDA tensors); seg_off m + 1 offsets on the HOST -> (m,) uint8 CUDA tensor"""
@@ -1086,6 +1106,34 @@ class Engine:
         st = self._chk(self.lib.c25519_precomp_msm_vartime(self.ctx, h, ss.ctypes.data, ss.shape[0], ds.ctypes.data, dp.ctypes.data, ds.shape[0],
                                                            in_fmt, out_fmt, out), (OK, NONE))
         return st, out.raw
+
+    def precomp_msm_vartime_rows(self, h, scalars, route=PRECOMP_ROWS_AUTO, out_fmt=FMT_EDWARDS_Y):
+        """many multiscalar muls over one precomputation in one call (VartimePrecomputedMultiscalarMul::vartime_multiscalar_mul per row,
+        traits.rs:304-419): out[r] = sum_j scalars[r][j] * S_j over the first w static points of the handle h.  scalars (m, w, 32) uint8 ->
+        (m, 32|160); every row in format 0 or 1 is byte for byte what precomp_msm_vartime returns for it alone.  route: PRECOMP_ROWS_AUTO
+        (precomp_msm_vartime_rows_plan tells which), or PRECOMP_ROWS_LANE / PRECOMP_ROWS_WAVE to force one.  The first call on a handle
+        builds its comb table (precomp_rows_table_bytes)."""
+        s = np.ascontiguousarray(scalars, dtype=np.uint8)
+        assert s.ndim == 3 and s.shape[2] == 32, "scalars must have shape (m, w, 32)"
+        m, w = s.shape[0], s.shape[1]
+        out = np.empty((m, _PT.get(out_fmt, 32)), np.uint8)
+        self._bind_stream()
+        self._chk(self.lib.c25519_precomp_msm_vartime_rows(self.ctx, h, s.ctypes.data, m, w, route, out_fmt, out.ctypes.data))
+        return out
+
+    @staticmethod
+    def precomp_msm_vartime_rows_plan(m, w):
+        """how PRECOMP_ROWS_AUTO routes m rows of w terms -> (route, waves launched): the lane route iff w < PRECOMP_ROWS_LANE_WIDTH and
+        m >= PRECOMP_ROWS_LANE_MIN_ROWS.  Host arithmetic: needs no GPU and no context (a static method); a shape the call would reject raises."""
+        plan = np.zeros(2, np.uint64)
+        st = load_library().c25519_precomp_msm_vartime_rows_plan(m, w, plan.ctypes.data)
+        if st < 0:
+            raise EngineError("HIP error %d: precomp_msm_vartime_rows_plan: m must be below 2^32 - 1 and m * w must not overflow" % -st)
+        return int(plan[0]), int(plan[1])
+
+    def precomp_rows_table_bytes(self, h):
+        """bytes of the handle's comb table: 0 until the first precomp_msm_vartime_rows call has built it, 65536 per static point afterwards"""
+        return int(self.lib.c25519_precomp_rows_table_bytes(h))
 
     def msm_consttime(self, scalars, points, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):
         s = _np8(scalars, 32); p = _np8(points, _PT[in_fmt])

@@ -544,6 +544,55 @@ uint64_t c25519_precomp_len(const c25519_precomp *p);
 int32_t c25519_precomp_msm_vartime(c25519_ctx *ctx, const c25519_precomp *p, const uint8_t *static_scalars, uint64_t n_static_scalars,
                                    const uint8_t *dyn_scalars, const uint8_t *dyn_points, uint64_t n_dyn, int in_fmt, int out_fmt, uint8_t *out);
 
+/* MANY multiscalar muls over ONE precomputation in one call: out[r] = sum_{j < w} scalars[r][j] * S_j over the first w static points of the
+ * handle, r < m -- one VartimePrecomputedMultiscalarMul::vartime_multiscalar_mul (traits.rs:304-419; edwards.rs:1037-1076, ristretto.rs:1004)
+ * per row: Pedersen / vector commitments to thousands of vectors, the generator side of thousands of Bulletproofs-size equations, polynomial
+ * commitments row by row.  Variable time: the scalars are public by contract, as for c25519_msm_vartime.
+ *   - scalars m x w x 32, row-major; out m x 32 | 160: HOST pointers in the un-suffixed form, DEVICE pointers in the _dev form.
+ *   - each of these returns -(hipErrorInvalidValue) before any launch: w above c25519_precomp_len (precomputed_straus.rs:86), out_fmt outside
+ *     0 .. 2, an unknown route, m not below 2^32 - 1, m * w overflowing, a handle of more than C25519_PRECOMP_ROWS_MAX_POINTS points (run such a
+ *     handle through c25519_precomp_msm_vartime, row by row).  m == 0 returns C25519_OK and touches nothing; w == 0 writes m identities.
+ *   - a scalar with bit 255 set, anywhere, returns -(hipErrorInvalidValue) with the message of c25519_msm_vartime; scalars need not be
+ *     reduced mod l.  There is no ok array: the static points were decoded at create, so the call returns C25519_OK or an error.
+ *   - both forms synchronise the context's stream once, at the end, to read the bit-255 verdict word.
+ *   - every out[r] in format 0 or 1 is byte for byte what c25519_precomp_msm_vartime returns for that row alone; a RAW160 output is the same
+ *     point (equal under ct_eq), not the same limbs.  Any out_fmt goes with any handle, as there.
+ * The comb table: the FIRST rows call on a handle computes e * 16^k * S_j for every static point j, window k < 64 and e = 1 .. 8 and keeps them
+ * resident as affine Niels records, the eight of one (j, k) next to each other: 65536 bytes per static point (256 MB at
+ * C25519_PRECOMP_ROWS_MAX_POINTS), owned by the handle and freed by c25519_precomp_destroy.  c25519_precomp_create, its footprint and the
+ * results of c25519_precomp_msm_vartime are unchanged; c25519_precomp_rows_table_bytes is 0 until that first call and the table's size after
+ * it.  The build runs on the context's stream, 256 static points at a time (20 MB of scratch); with the allocation it adds 0.7 / 2.7 / 10.5 ms to
+ * that first call for 128 / 1024 / 4096 points.
+ * A handle is used from one thread at a time, like its context.
+ * Cost: a row needs no doubling and no per-call table -- at most 64 mixed additions per term (radix-16 signed digits, scalar.rs:1019-1051; a
+ * zero digit is skipped), which no doubling chain orders.  Two routes, chosen by (m, w) alone (c25519_precomp_msm_vartime_rows_plan reports it;
+ * route = C25519_PRECOMP_ROWS_LANE / _WAVE forces one, and both are correct for every shape):
+ *   - LANE: one GPU lane per row, 64 consecutive rows per wave, all on the same (j, k) at the same time so that their gathers fall into one
+ *     1 KB group of records; 64 w serial additions per lane, so it needs tens of thousands of rows to fill the GPU.
+ *   - WAVE: one wave per row, lane l takes window l of every scalar; the 64 partial sums are folded with six shuffle rounds: w + about 8
+ *     addition slots per row.
+ *   C25519_PRECOMP_ROWS_AUTO takes the lane route iff w < C25519_PRECOMP_ROWS_LANE_WIDTH and m >= C25519_PRECOMP_ROWS_LANE_MIN_ROWS, both set
+ *   at the crossover measured by tools/precomp_rows_numbers.py (profiles/precomp_rows_numbers.txt).
+ * Measured against one c25519_precomp_msm_vartime per row (0.16 - 0.19 ms each) and against c25519_msm_vartime_segments_dev with the
+ * generators replicated into every row: 4096 rows of 128 scalars 1.46 ms against 670 and 3.86 ms; 131072 rows of 2: 0.78 ms against 22 s and
+ * 2.08 ms; 64 rows of 2048: 6.99 ms against 11.9 and 7.04 ms -- LEVEL with the segments call there (x1.01): 64 waves do not fill the GPU, and a
+ * row is one wave's chain of w additions however few rows there are. */
+#define C25519_PRECOMP_ROWS_MAX_POINTS 4096   /* largest handle the rows call serves: 64 KB of comb table per point, 256 MB */
+#define C25519_PRECOMP_ROWS_AUTO 0
+#define C25519_PRECOMP_ROWS_LANE 1            /* one lane per row  */
+#define C25519_PRECOMP_ROWS_WAVE 2            /* one wave per row  */
+#define C25519_PRECOMP_ROWS_LANE_WIDTH 16     /* AUTO: the lane route only for rows narrower than this ... */
+#define C25519_PRECOMP_ROWS_LANE_MIN_ROWS 32768   /* ... and only from this many rows (measured: DESIGN.md section 3.15) */
+int32_t c25519_precomp_msm_vartime_rows_dev(c25519_ctx *ctx, c25519_precomp *p, const uint8_t *d_scalars /* m x w x 32, row-major */, uint64_t m, uint64_t w,
+                                            int32_t route, int out_fmt, uint8_t *d_out /* m x (32 | 160) */);
+int32_t c25519_precomp_msm_vartime_rows(c25519_ctx *ctx, c25519_precomp *p, const uint8_t *scalars, uint64_t m, uint64_t w, int32_t route, int out_fmt,
+                                        uint8_t *out);
+/* how C25519_PRECOMP_ROWS_AUTO routes m rows of w terms: plan[0] the route (C25519_PRECOMP_ROWS_LANE or _WAVE), plan[1] the waves it launches.
+ * Same bounds on m and m * w and the same error as the call.  Host arithmetic: no context, no GPU. */
+int32_t c25519_precomp_msm_vartime_rows_plan(uint64_t m, uint64_t w, uint64_t plan[2]);
+/* bytes of the handle's comb table: 0 until the first rows call has built it, 65536 per static point afterwards */
+uint64_t c25519_precomp_rows_table_bytes(const c25519_precomp *p);
+
 /* ---- regular-schedule multiscalar multiplication: MultiscalarMul::multiscalar_mul ------------------------
  * replaces backend::straus_multiscalar_mul (backend.rs:196 -> scalar_mul/straus.rs:103-144;
  * edwards.rs:966-1000).  One radix-16 fixed-window ladder per term (the schedule of variable_base.rs: identical
