@@ -38,8 +38,7 @@ using namespace c25519;
 
 namespace c25519 {
 
-constexpr int ROWS_ENT = 8;                                 // records per window (1 .. 8 times the window's base); ROWS_WIN windows per scalar: rows_digits.h
-constexpr u64 ROWS_REC = (u64)ROWS_WIN * ROWS_ENT;          // records per static point: 512 x 128 bytes
+// (ROWS_WIN, ROWS_ENT, ROWS_REC: rows_digits.h, shared with mid_mixed.hip)
 enum { ROWS_FLAG_BIT255 = 1 };                              // the verdict word at d_flag (the word mid_seg.hip uses for the same verdict)
 
 // ---- the comb table ---------------------------------------------------------------------------------------------------------------
@@ -168,8 +167,9 @@ static int32_t rows_check(c25519_ctx *ctx, const c25519_precomp *p, uint64_t m, 
     return C25519_OK;
 }
 
-// the comb table of the handle, once: enqueued on the context's stream in front of the first rows kernel
-static int32_t rows_build(c25519_ctx *ctx, c25519_precomp *p) {
+// the comb table of the handle, once: enqueued on the context's stream in front of the first rows kernel (precomp.h: the mixed rows call of
+// mid_mixed.hip builds it through this function too)
+int32_t rows_build(c25519_ctx *ctx, c25519_precomp *p) {
     if (p->rows_bytes || p->n == 0) return C25519_OK;
     hipStream_t st = ctx->stream;
     const uint64_t n = p->n, chunk = std::min<uint64_t>(n, ROWS_BUILD_CHUNK);

@@ -1,5 +1,5 @@
-// The handle of the precomputed-static calls (c25519_precomp_*), shared by extra.hip (create, destroy, len, the bucket call) and mid_rows.hip (the
-// rows call and its comb table).  A handle is used from one thread at a time, like its context.
+// The handle of the precomputed-static calls (c25519_precomp_*), shared by extra.hip (create, destroy, len, the bucket call), mid_rows.hip (the
+// rows call and its comb table) and mid_mixed.hip (the mixed rows call over the same comb table).  A handle is used from one thread at a time, like its context.
 #pragma once
 #include <stdint.h>
 #include "msm_internal.h"
@@ -13,3 +13,6 @@ struct c25519_precomp {
     uint32_t *d_rows = nullptr;
     uint64_t rows_bytes = 0;
 };
+
+// mid_rows.hip: builds the comb table on the context's stream if the handle has none yet (it reserves its scratch in ctx->tmp_f)
+int32_t rows_build(c25519_ctx *ctx, c25519_precomp *p);

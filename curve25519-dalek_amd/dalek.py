@@ -16,6 +16,8 @@ error behaviour), batched, on top of Engine.  Reference entry points mirrored:
   VartimeRistrettoPrecomputation              curve25519-dalek/src/ristretto.rs:1004
   Vartime{Edwards,Ristretto}Precomputation::vartime_multiscalar_mul, many rows of scalars over one precomputation in one call
                                               traits.rs:304-419   (vartime_multiscalar_mul_many)
+  Vartime{Edwards,Ristretto}Precomputation::vartime_mixed_multiscalar_mul, many rows of static scalars plus each row's own dynamic terms in one call
+                                              traits.rs:304-419, precomputed_straus.rs:29-127   (vartime_mixed_multiscalar_mul_many)
   RistrettoPoint::double_and_compress_batch   curve25519-dalek/src/ristretto.rs:564
   Scalar::invert_batch                        curve25519-dalek/src/scalar.rs:802
   EdwardsBasepointTable::create / mul_base    curve25519-dalek/src/edwards.rs:1131-1141 / :1192-1209   (any basepoint)
@@ -707,6 +709,22 @@ class VartimeEdwardsPrecomputation:
         s = _cat([x for r in rows for x in r], 32).reshape(len(rows), w, 32)
         out = self.eng.precomp_msm_vartime_rows(self.h, s, _e.PRECOMP_ROWS_AUTO, self._fmt)
         return [out[i].tobytes() for i in range(out.shape[0])]
+
+    def vartime_mixed_multiscalar_mul_many(self, rows):
+        """[vartime_mixed_multiscalar_mul(*row)] for every row in ONE call: rows is a list of (static_scalars, dynamic_scalars, dynamic_points)
+        -> a list with the 32-byte encoding per row, or None where a dynamic point of that row does not decode.  Rows of unequal static width
+        are zero-padded to the widest (a zero scalar adds nothing); a row may have at most engine.MSM_SEGMENT_WAVE_MAX dynamic terms (call
+        vartime_mixed_multiscalar_mul for a longer one).  The comb table is the one vartime_multiscalar_mul_many builds."""
+        rows = [(list(a), list(b), list(c)) for a, b, c in rows]
+        if any(len(b) != len(c) for _, b, c in rows):
+            raise AssertionError("dynamic scalars and points must have equal length")   # precomputed_straus.rs:87
+        w = max([len(a) for a, _, _ in rows], default=0)
+        zero = bytes(32)
+        ss = _cat([x for a, _, _ in rows for x in a + [zero] * (w - len(a))], 32).reshape(len(rows), w, 32)
+        off = np.cumsum([0] + [len(b) for _, b, _ in rows]).astype(np.uint64)
+        st, out, ok = self.eng.precomp_msm_vartime_mixed_rows(self.h, ss, _cat([x for _, b, _ in rows for x in b], 32), _cat([x for _, _, c in rows for x in c], 32),
+                                                              off, self._fmt, _e.PRECOMP_ROWS_AUTO, self._fmt)
+        return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
 
     def close(self):
         if self.h:

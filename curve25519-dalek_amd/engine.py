@@ -131,6 +131,9 @@ _SIGS = {
     "c25519_precomp_msm_vartime_rows": (_i32, [_vp, _vp, _vp, _u64, _u64, _i32, C.c_int, _vp]),
     "c25519_precomp_msm_vartime_rows_plan": (_i32, [_u64, _u64, _vp]),
     "c25519_precomp_rows_table_bytes": (_u64, [_vp]),
+    "c25519_precomp_msm_vartime_mixed_rows_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, C.c_int, _vp, _i32, C.c_int, _vp, _vp]),
+    "c25519_precomp_msm_vartime_mixed_rows": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, C.c_int, _vp, _i32, C.c_int, _vp, _vp]),
+    "c25519_precomp_msm_vartime_mixed_rows_plan": (_i32, [_u64, _u64, _vp, _vp]),
     "c25519_msm_consttime": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "c25519_double_and_compress_batch_dev": (_i32, [_vp, _vp, _u64, _vp]),
     "c25519_double_and_compress_batch": (_i32, [_vp, _vp, _u64, _vp]),
@@ -220,6 +223,9 @@ PRECOMP_ROWS_MAX_POINTS = 4096   # C25519_PRECOMP_ROWS_MAX_POINTS: the largest h
 PRECOMP_ROWS_AUTO, PRECOMP_ROWS_LANE, PRECOMP_ROWS_WAVE = 0, 1, 2      # C25519_PRECOMP_ROWS_*: its route argument (one lane / one wave per row)
 PRECOMP_ROWS_LANE_WIDTH = 16     # C25519_PRECOMP_ROWS_LANE_WIDTH: AUTO takes the lane route only for rows narrower than this ...
 PRECOMP_ROWS_LANE_MIN_ROWS = 32768       # C25519_PRECOMP_ROWS_LANE_MIN_ROWS: ... and only from this many rows
+PRECOMP_MIXED_LANE_DYN_MAX = 16  # C25519_PRECOMP_MIXED_LANE_DYN_MAX: precomp_msm_vartime_mixed_rows AUTO takes the lane route only if no row has more dynamic terms ...
+PRECOMP_MIXED_LANE_BASE_ROWS = 1024      # C25519_PRECOMP_MIXED_LANE_BASE_ROWS: ... and only from BASE_ROWS + ROWS_PER_TERM * (w + the longest row's dynamic terms) rows
+PRECOMP_MIXED_LANE_ROWS_PER_TERM = 320   # C25519_PRECOMP_MIXED_LANE_ROWS_PER_TERM
 
 
 def _seg_off_host(seg_off):
@@ -733,6 +739,29 @@ class Engine:
         self._chk(self.lib.c25519_precomp_msm_vartime_rows_dev(self.ctx, h, scalars.data_ptr(), m, w, route, out_fmt, out.data_ptr()))
         return out
 
+    def precomp_msm_vartime_mixed_rows_t(self, h, static_scalars, dyn_scalars, dyn_points, dyn_off, in_fmt=FMT_RAW160, route=PRECOMP_ROWS_AUTO, out_fmt=FMT_EDWARDS_Y):
+        """many mixed multiscalar muls over one precomputation: out[r] = sum_j static_scalars[r][j] * S_j + sum dyn_scalars[i] * dyn_points[i] over
+        i in [dyn_off[r], dyn_off[r+1]).  static_scalars (m, w, 32), dyn_scalars (n_dyn, 32), dyn_points (n_dyn, 32|160) uint8 CUDA tensors; dyn_off
+        m + 1 offsets on the HOST (a sequence or a CPU tensor: the lengths are public and the host cuts the passes by them) -> (status OK | NONE,
+        (m, 32|160), ok (m,)), on torch's current stream (the call synchronises it once)"""
+        assert static_scalars.dim() == 3 and static_scalars.shape[2] == 32, "static_scalars must have shape (m, w, 32)"
+        m, w = int(static_scalars.shape[0]), int(static_scalars.shape[1])
+        if static_scalars.numel():
+            self._t(static_scalars, 32)
+        n = self._t(dyn_scalars, 32)
+        assert self._t(dyn_points, _PT.get(in_fmt, 32)) == n
+        if hasattr(dyn_off, "is_cuda"):
+            assert not dyn_off.is_cuda, "dyn_off stays on the host"
+            dyn_off = dyn_off.numpy()
+        off = np.ascontiguousarray(np.asarray(dyn_off, dtype=np.uint64).reshape(-1))
+        assert off.shape[0] == m + 1, "dyn_off must hold m + 1 offsets"
+        out = self.torch.empty((m, _PT.get(out_fmt, 32)), dtype=self.torch.uint8, device=self.device)
+        ok = self.torch.empty((m,), dtype=self.torch.uint8, device=self.device)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_precomp_msm_vartime_mixed_rows_dev(self.ctx, h, static_scalars.data_ptr(), m, w, dyn_scalars.data_ptr(), dyn_points.data_ptr(), n,
+                                                                          in_fmt, off.ctypes.data, route, out_fmt, out.data_ptr(), ok.data_ptr()), (OK, NONE))
+        return st, out, ok
+
     def verify_batch_segments_t(self, msgs, msg_off, sigs, pks, seg_off, z_mode=Z_TRANSCRIPT, pk_points=None):
         """many independent verify_batch calls in one: status[s] is what verify_batch_t returns for signatures [seg_off[s], seg_off[s+1]) alone.
         msgs, msg_off, sigs, pks, pk_points as for verify_batch_t (CUDA tensors); seg_off m + 1 offsets on the HOST -> (m,) uint8 CUDA tensor"""
@@ -1134,6 +1163,45 @@ class Engine:
     def precomp_rows_table_bytes(self, h):
         """bytes of the handle's comb table: 0 until the first precomp_msm_vartime_rows call has built it, 65536 per static point afterwards"""
         return int(self.lib.c25519_precomp_rows_table_bytes(h))
+
+    def precomp_msm_vartime_mixed_rows(self, h, static_scalars, dyn_scalars, dyn_points, dyn_off, in_fmt=FMT_RAW160, route=PRECOMP_ROWS_AUTO, out_fmt=FMT_EDWARDS_Y):
+        """many mixed multiscalar muls over one precomputation in one call (VartimePrecomputedMultiscalarMul::vartime_mixed_multiscalar_mul per
+        row, traits.rs:304-419, precomputed_straus.rs:29-127): out[r] = sum_j static_scalars[r][j] * S_j over the first w static points of the
+        handle h + sum dyn_scalars[i] * dyn_points[i] over i in [dyn_off[r], dyn_off[r+1]).  static_scalars (m, w, 32), dyn_scalars (n_dyn, 32),
+        dyn_points (n_dyn, 32|160) uint8, dyn_off m + 1 offsets -> (status OK | NONE, (m, 32|160), ok (m,)); ok[r] = 0 where a dynamic point of
+        row r does not decode.  Every row with ok = 1 in format 0 or 1 is byte for byte what precomp_msm_vartime returns for it alone; a row
+        may have at most MSM_SEGMENT_WAVE_MAX dynamic terms.  route: PRECOMP_ROWS_AUTO (precomp_msm_vartime_mixed_rows_plan tells which),
+        or PRECOMP_ROWS_LANE / PRECOMP_ROWS_WAVE to force one.  The comb table is the rows call's (precomp_rows_table_bytes)."""
+        ss = np.ascontiguousarray(static_scalars, dtype=np.uint8)
+        assert ss.ndim == 3 and ss.shape[2] == 32, "static_scalars must have shape (m, w, 32)"
+        m, w = ss.shape[0], ss.shape[1]
+        ds = _np8(dyn_scalars, 32) if len(dyn_scalars) else np.zeros((0, 32), np.uint8)
+        dp = _np8(dyn_points, _PT.get(in_fmt, 32)) if len(dyn_points) else np.zeros((0, _PT.get(in_fmt, 32)), np.uint8)
+        assert ds.shape[0] == dp.shape[0]
+        off = np.ascontiguousarray(np.asarray(dyn_off, dtype=np.uint64).reshape(-1))
+        assert off.shape[0] == m + 1, "dyn_off must hold m + 1 offsets"
+        out = np.empty((m, _PT.get(out_fmt, 32)), np.uint8); ok = np.empty((m,), np.uint8)
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_precomp_msm_vartime_mixed_rows(self.ctx, h, ss.ctypes.data, m, w, ds.ctypes.data, dp.ctypes.data, ds.shape[0], in_fmt,
+                                                                      off.ctypes.data, route, out_fmt, out.ctypes.data, ok.ctypes.data), (OK, NONE))
+        return st, out, ok
+
+    @staticmethod
+    def precomp_msm_vartime_mixed_rows_plan(m, w, dyn_off):
+        """how precomp_msm_vartime_mixed_rows treats m rows of w static scalars with these m + 1 dynamic offsets -> (the route PRECOMP_ROWS_AUTO
+        takes, waves of its row launches, passes, most dynamic terms in one pass): for w < PRECOMP_ROWS_LANE_WIDTH the lane route iff no row has more
+        than PRECOMP_MIXED_LANE_DYN_MAX dynamic terms and m >= PRECOMP_MIXED_LANE_BASE_ROWS + PRECOMP_MIXED_LANE_ROWS_PER_TERM * (w + the longest
+        row's dynamic terms) -- without any dynamic term the rule of precomp_msm_vartime_rows_plan; a pass holds at most MSM_SEGMENT_PASS_TERMS
+        dynamic terms.  Host arithmetic: needs no GPU and no context (a static method); a shape the call would
+        reject raises."""
+        off = np.ascontiguousarray(np.asarray(dyn_off, dtype=np.uint64).reshape(-1))
+        assert m == 0 or off.shape[0] == m + 1, "dyn_off must hold m + 1 offsets"
+        plan = np.zeros(4, np.uint64)
+        st = load_library().c25519_precomp_msm_vartime_mixed_rows_plan(m, w, off.ctypes.data if off.size else None, plan.ctypes.data)
+        if st < 0:
+            raise EngineError("HIP error %d: precomp_msm_vartime_mixed_rows_plan: m must be below 2^32 - 1, m * w must not overflow, dyn_off must be m + 1 "
+                              "non-decreasing values from 0, below 2^40, and no row may have more than MSM_SEGMENT_WAVE_MAX dynamic terms" % -st)
+        return tuple(int(x) for x in plan)
 
     def msm_consttime(self, scalars, points, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):
         s = _np8(scalars, 32); p = _np8(points, _PT[in_fmt])

@@ -593,6 +593,67 @@ int32_t c25519_precomp_msm_vartime_rows_plan(uint64_t m, uint64_t w, uint64_t pl
 /* bytes of the handle's comb table: 0 until the first rows call has built it, 65536 per static point afterwards */
 uint64_t c25519_precomp_rows_table_bytes(const c25519_precomp *p);
 
+/* MANY MIXED multiscalar muls over ONE precomputation in one call:
+ *   out[r] = sum_{j < w} static_scalars[r][j] * S_j + sum_{i in [dyn_off[r], dyn_off[r+1])} dyn_scalars[i] * dyn_points[i],   r < m
+ * -- one VartimePrecomputedMultiscalarMul::vartime_mixed_multiscalar_mul (traits.rs:304-419, precomputed_straus.rs:29-127) per row: the
+ * verification equation of a Bulletproofs range proof (2 * 64 + 2 static generators, 17 dynamic points A, S, T1, T2, V, L_i, R_i), of an
+ * aggregated one, of a Schnorr / DLEQ / Pedersen-opening check (1 - 2 static, 1 - 3 dynamic).  Variable time: the scalars are public by
+ * contract, as for c25519_msm_vartime.
+ *   - static_scalars m x w x 32, row-major; dyn_scalars n_dyn x 32, dyn_points n_dyn x 32 | 160 in in_fmt, the rows' terms one after the other;
+ *     out m x 32 | 160; ok m bytes (may be NULL): HOST pointers in the un-suffixed form, DEVICE pointers in the _dev form.  dyn_off is a HOST
+ *     array of m + 1 offsets in both forms, as for c25519_msm_vartime_segments_dev: the lengths are public and the host cuts the passes by them.
+ *   - each of these returns -(hipErrorInvalidValue) before any launch: what c25519_precomp_msm_vartime_rows refuses (w above c25519_precomp_len,
+ *     precomputed_straus.rs:86; out_fmt outside 0 .. 2; an unknown route; m not below 2^32 - 1; m * w overflowing; a handle of more than
+ *     C25519_PRECOMP_ROWS_MAX_POINTS points); offsets c25519_msm_vartime_segments refuses (dyn_off[0] != 0, dyn_off[m] != n_dyn, a decreasing
+ *     pair, n_dyn not below 2^40); in_fmt and out_fmt of different groups (the pairing rule of c25519_msm_vartime_segments); and a row of more
+ *     than C25519_MSM_SEGMENT_WAVE_MAX dynamic terms -- such a row belongs to c25519_precomp_msm_vartime, one call for it.
+ *   - m == 0 returns C25519_OK and touches nothing; a row with w == 0 and no dynamic term is the identity with ok = 1.
+ *   - a static or dynamic scalar with bit 255 set, anywhere, returns -(hipErrorInvalidValue) with the message of c25519_msm_vartime; scalars
+ *     need not be reduced mod l.
+ *   - ok[r] = 0 iff a dynamic point of row r does not decode (Option::None of that row alone; its output is unspecified); the call returns
+ *     C25519_NONE iff any row has ok = 0 and C25519_OK otherwise, with or without an ok array.  RAW160 dynamic points are trusted.
+ *   - both forms synchronise the context's stream once, at the end, to read the two verdict words.
+ *   - every out[r] with ok[r] = 1 in format 0 or 1 is byte for byte what c25519_precomp_msm_vartime returns for that row alone; a RAW160
+ *     output is the same point (equal under ct_eq), not the same limbs.
+ * The comb table is the rows call's: the first mixed OR rows call on a handle builds it (65536 bytes per static point, see above), and
+ * c25519_precomp_rows_table_bytes reports it as before.
+ * How: the dynamic half of a row is Straus with one doubling chain shared by its terms (scalar_mul/straus.rs:159-200), over per-term tables
+ * {1 .. 8} P built per pass as by c25519_msm_vartime_segments (1344 bytes per term; at most C25519_MSM_SEGMENT_PASS_TERMS dynamic terms are
+ * resident at a time, more are cut into passes at row boundaries: one tables launch and one row launch per pass).  The static half needs no
+ * doubling -- the comb records are already scaled by 16^k -- so it is added into the accumulator the window loop leaves behind: one
+ * accumulator, one fold and one store per row, where the composition rows -> segments -> c25519_point_add_batch_dev takes three calls, three
+ * synchronisations and two 160-byte round trips per row.  A row without dynamic terms skips the doubling chain.  Two routes
+ * (route = C25519_PRECOMP_ROWS_LANE / _WAVE forces one; both are correct for every accepted shape):
+ *   - WAVE: one wave per row; lane l takes dynamic terms l, l + 64, ... through the window loop, then window l of every static scalar.
+ *   - LANE: one lane per row, 64 consecutive rows per wave: a wave costs what its longest row costs.
+ *   C25519_PRECOMP_ROWS_AUTO (c25519_precomp_msm_vartime_mixed_rows_plan reports it), with t = w + the dynamic terms of the longest row: the
+ *   wave route if w >= C25519_PRECOMP_ROWS_LANE_WIDTH; the rule of the rows call (lane iff m >= C25519_PRECOMP_ROWS_LANE_MIN_ROWS) if no row has
+ *   a dynamic term -- the call is the rows call then; otherwise the lane route iff the longest row has at most
+ *   C25519_PRECOMP_MIXED_LANE_DYN_MAX dynamic terms and m >= C25519_PRECOMP_MIXED_LANE_BASE_ROWS + C25519_PRECOMP_MIXED_LANE_ROWS_PER_TERM * t.
+ *   Measured, not derived: with a dynamic term the wave route pays a whole doubling chain per row, so lanes win from far fewer rows than in
+ *   the rows call, and a lane's gathers over long rows' tables lose to the wave route well below C25519_MSM_SEGMENT_DIRECT_MAX terms.
+ * Measured by tools/precomp_mixed_numbers.py (profiles/precomp_mixed_numbers.txt): against the three
+ * calls it replaces (rows -> segments -> c25519_point_add_batch_dev) and one c25519_precomp_msm_vartime per row, device-resident, ms:
+ * 4096 rows of 130 + 17: 3.82 against 5.51 and 2030; 256 of 2050 + 40: 6.68 against 15.2 and 109; 64 of 2048 + 64: 6.67 against 19.4 and 27;
+ * 131072 of 2 + 1: 2.38 against 2.31 and 42 500; 2^20 of 1 + 2: 18.3 against 18.6 and 337 000 -- LEVEL with the composition at those two;
+ * 4096 of 2 + 1: 1.17 against 0.98 and 1310 -- x1.2 SLOWER than the composition.  Rows of one to three terms are the same lane work
+ * either way: there the call saves the caller two calls, not time. */
+#define C25519_PRECOMP_MIXED_LANE_DYN_MAX 16          /* AUTO: the lane route only if no row has more dynamic terms than this ... */
+#define C25519_PRECOMP_MIXED_LANE_BASE_ROWS 1024      /* ... and only from BASE_ROWS + ROWS_PER_TERM * (w + longest row's dynamic terms) rows */
+#define C25519_PRECOMP_MIXED_LANE_ROWS_PER_TERM 320   /*     (measured: DESIGN.md section 3.16) */
+int32_t c25519_precomp_msm_vartime_mixed_rows_dev(c25519_ctx *ctx, c25519_precomp *p, const uint8_t *d_static_scalars /* m x w x 32, row-major */, uint64_t m,
+                                                  uint64_t w, const uint8_t *d_dyn_scalars /* n_dyn x 32 */, const uint8_t *d_dyn_points /* n_dyn x (32 | 160) */,
+                                                  uint64_t n_dyn, int in_fmt, const uint64_t *dyn_off /* m + 1 HOST offsets */, int32_t route, int out_fmt,
+                                                  uint8_t *d_out /* m x (32 | 160) */, uint8_t *d_ok /* m, may be NULL */);
+int32_t c25519_precomp_msm_vartime_mixed_rows(c25519_ctx *ctx, c25519_precomp *p, const uint8_t *static_scalars, uint64_t m, uint64_t w, const uint8_t *dyn_scalars,
+                                              const uint8_t *dyn_points, uint64_t n_dyn, int in_fmt, const uint64_t *dyn_off, int32_t route, int out_fmt, uint8_t *out,
+                                              uint8_t *ok);
+/* how the mixed rows call treats m rows of w static scalars with these dynamic offsets: plan[0] the route C25519_PRECOMP_ROWS_AUTO takes,
+ * plan[1] the waves of its row launches summed over the passes, plan[2] the passes, plan[3] the most dynamic terms in one pass.  Same
+ * refusals and the same error as the call, as far as they depend on (m, w, dyn_off); n_dyn is dyn_off[m], read only once m is known to be
+ * below 2^32 - 1.  Host arithmetic: no context, no GPU. */
+int32_t c25519_precomp_msm_vartime_mixed_rows_plan(uint64_t m, uint64_t w, const uint64_t *dyn_off, uint64_t plan[4]);
+
 /* ---- regular-schedule multiscalar multiplication: MultiscalarMul::multiscalar_mul ------------------------
  * replaces backend::straus_multiscalar_mul (backend.rs:196 -> scalar_mul/straus.rs:103-144;
  * edwards.rs:966-1000).  One radix-16 fixed-window ladder per term (the schedule of variable_base.rs: identical
