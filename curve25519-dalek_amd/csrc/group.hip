@@ -218,12 +218,7 @@ __global__ void __launch_bounds__(256) k_seg_finish(const u64 *__restrict__ seg_
 }  // namespace c25519
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-// the format rule of every call here: Edwards in (0) -> 0 or 2, Ristretto in (1) -> 1 or 2, RAW160 in (2) -> anything
-static bool grp_pair_ok(int in_fmt, int out_fmt) {
-    if (in_fmt == C25519_FMT_EDWARDS_Y) return ed_fmt_ok(out_fmt);
-    if (in_fmt == C25519_FMT_RISTRETTO) return ris_fmt_ok(out_fmt);
-    return in_fmt == C25519_FMT_RAW160 && (ed_fmt_ok(out_fmt) || out_fmt == C25519_FMT_RISTRETTO);
-}
+// (the format rule of every call here: capi_util.h fmt_pair_ok)
 static inline bool grp_compressed(int in_fmt) { return in_fmt != C25519_FMT_RAW160; }
 
 template <int OP, int IN>
@@ -318,12 +313,12 @@ static int32_t elem_host(c25519_ctx *ctx, const uint8_t *p, const uint8_t *q, ui
 
 static int32_t add_check(c25519_ctx *ctx, int op, int in_fmt, int out_fmt) {
     if (op != C25519_POINT_ADD && op != C25519_POINT_SUB) return bad_arg(ctx, "point_add: op must be C25519_POINT_ADD or C25519_POINT_SUB");
-    if (!grp_pair_ok(in_fmt, out_fmt)) return bad_arg(ctx, "point_add: in_fmt and out_fmt must belong to one group");
+    if (!fmt_pair_ok(in_fmt, out_fmt)) return bad_arg(ctx, "point_add: in_fmt and out_fmt must belong to one group");
     return C25519_OK;
 }
 static int32_t map_check(c25519_ctx *ctx, int op, int in_fmt, int out_fmt) {
     if (op != C25519_POINT_NEG && op != C25519_POINT_MUL_BY_COFACTOR) return bad_arg(ctx, "point_map: op must be C25519_POINT_NEG or C25519_POINT_MUL_BY_COFACTOR");
-    if (!grp_pair_ok(in_fmt, out_fmt)) return bad_arg(ctx, "point_map: in_fmt and out_fmt must belong to one group");
+    if (!fmt_pair_ok(in_fmt, out_fmt)) return bad_arg(ctx, "point_map: in_fmt and out_fmt must belong to one group");
     if (op == C25519_POINT_MUL_BY_COFACTOR && (in_fmt == C25519_FMT_RISTRETTO || out_fmt == C25519_FMT_RISTRETTO))
         return bad_arg(ctx, "point_map: mul_by_cofactor is an Edwards operation");
     return C25519_OK;
@@ -409,8 +404,6 @@ EXPORT int32_t c25519_point_eq_batch(c25519_ctx *ctx, const uint8_t *p, const ui
 }
 
 // ---- segmented sum --------------------------------------------------------------------------------------------------------------
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int32_t sum_enqueue(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n, int in_fmt, const uint64_t *d_seg_off, uint64_t m, int out_fmt, uint8_t *d_sums,
                            uint8_t *d_ok) {
     hipStream_t st = ctx->stream;
@@ -458,7 +451,7 @@ static int32_t sum_enqueue(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n,
     return r ? r : grp_flag_bad(ctx, in_fmt, okbuf, m);
 }
 static int32_t sum_check(c25519_ctx *ctx, int in_fmt, uint64_t m, int out_fmt) {
-    if (!grp_pair_ok(in_fmt, out_fmt)) return bad_arg(ctx, "point_sum_segments: in_fmt and out_fmt must belong to one group");
+    if (!fmt_pair_ok(in_fmt, out_fmt)) return bad_arg(ctx, "point_sum_segments: in_fmt and out_fmt must belong to one group");
     if (m >= KEY_NONE) return bad_arg(ctx, "point_sum_segments: m must be below 2^32 - 1");
     return C25519_OK;
 }

@@ -11,12 +11,12 @@
 //                          160-byte points (slot e = 1 of every (j, k))
 //   k_mid_rows_multiples   one lane per (j, k): e * 16^k S_j for e = 2 .. 8 by repeated addition; prep_points (the MSM's own normaliser) turns
 //                          the raw points into the records
-//   k_mid_rows_lane        one LANE per row, the 64 lanes of a wave are 64 consecutive rows: for every j the scalar is recoded in registers, then
-//                          for every window the record (j, k, |d|) is added or subtracted.  All lanes of a wave are on the same (j, k) at the
-//                          same time: their gathers fall into one 1 KB group of records.
-//   k_mid_rows_wave        one WAVE per row, lane l is window l: for every j each lane takes its own digit of the scalar (a uniform load) and
-//                          adds record (j, l, |d|); the 64 partial sums are folded across the wave with six shuffle rounds.
-// Digits (rows_digits.h) as k_mid_seg_tables makes them (scalar.rs:1019-1051): nibble k of s' = s + 0x0888...8 minus 8, the top nibble left unsigned (0 .. 8); no
+//   k_mid_rows_lane        one LANE per row, the 64 lanes of a wave are 64 consecutive rows (straus.h straus_comb_lane): for every j the scalar is
+//                          recoded in registers, then for every window the record (j, k, |d|) is added or subtracted.  All lanes of a wave are
+//                          on the same (j, k) at the same time: their gathers fall into one 1 KB group of records.
+//   k_mid_rows_wave        one WAVE per row, lane l is window l (straus_comb_wave): for every j each lane takes its own digit of the scalar (a
+//                          uniform load) and adds record (j, l, |d|); the 64 partial sums are folded across the wave with six shuffle rounds.
+// Digits (rows_digits.h) as k_mid_straus_tables makes them (scalar.rs:1019-1051): nibble k of s' = s + 0x0888...8 minus 8, the top nibble left unsigned (0 .. 8); no
 // digit array is written.  Complete formulas (ge_madd_signed_p3, ge_add): no special case for identity, equal or opposite operands; a zero
 // digit is skipped.  The scalars are public by contract (a *_vartime entry point): branches and table addresses depend on their digits.
 // Every loop bound comes from the m and w the host validated; the kernels wait for nothing and use no atomics (the verdict word is set by a
@@ -24,22 +24,15 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <string.h>
-#include "../../include/c25519_hip.h"
-#include "devio.h"
-#include "kernels.h"
-#include "ctx.h"
 #include "msm_internal.h"
-#include "precomp.h"
-#include "rows_digits.h"
+#include "straus.h"                         // (and through it devio.h, kernels.h, ctx.h, knobs.h, precomp.h, rows_digits.h, capi_util.h)
 #include "ffi.h"
-#include "capi_util.h"
 
 using namespace c25519;
 
 namespace c25519 {
 
-// (ROWS_WIN, ROWS_ENT, ROWS_REC: rows_digits.h, shared with mid_mixed.hip)
-enum { ROWS_FLAG_BIT255 = 1 };                              // the verdict word at d_flag (the word mid_seg.hip uses for the same verdict)
+// (ROWS_WIN, ROWS_ENT, ROWS_REC: rows_digits.h; the loops over the comb table and the verdict words: straus.h, shared with mid_mixed.hip)
 
 // ---- the comb table ---------------------------------------------------------------------------------------------------------------
 // Static points [j0, j0 + cnt) of the handle -> raw[((j - j0) * 64 + k) * 8] = 16^k S_j.  S_j = (2x : 2y : 2 : 2xy) from its window-0 record.
@@ -74,30 +67,7 @@ __global__ void __launch_bounds__(256) k_mid_rows_lane(const uint8_t *__restrict
     const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= m) return;
     ge_p3 acc = ge_identity();
-#pragma unroll 1
-    for (u32 j = 0; j < w; j++) {
-        u32 s[8];
-        load8(scalars, r * w + j, s);
-        if (rows_recode(s)) flags[ROWS_FLAG_BIT255] = 1u;
-        const u64 base = (u64)j * ROWS_REC;
-        u32 cur = s[0];
-#pragma unroll 1
-        for (int k = 0; k < ROWS_WIN; k++) {
-            const u32 nib = cur & 15u;
-            cur >>= 4;
-            if ((k & 7) == 7) {                              // the next word moves down: no register array is indexed by k
-                for (int q = 0; q < 7; q++) s[q] = s[q + 1];
-                cur = s[0];
-            }
-            const int dg = rows_digit(nib, k);
-            if (dg != 0) {
-                const bool neg = dg < 0;
-                const u32 mag = (u32)(neg ? -dg : dg);                      // 1 .. 8
-                acc = ge_madd_signed_p3(acc, pts_load(tab, base + (u64)k * ROWS_ENT + ((mag - 1u) & 7u)), neg);
-            }
-            ge_pin(acc);
-        }
-    }
+    straus_comb_lane(acc, scalars, r * w, w, tab, flags);
     raw160_store(out_raw, r, acc);
 }
 
@@ -107,42 +77,23 @@ __global__ void __launch_bounds__(256) k_mid_rows_wave(const uint8_t *__restrict
                                                        u32 *__restrict__ flags) {
     const u32 r = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
     if (r >= m) return;
-    const u32 lane = threadIdx.x & 63u, word = lane >> 3, shift = 4u * (lane & 7u);
+    const u32 lane = threadIdx.x & 63u;
     ge_p3 acc = ge_identity();
-#pragma unroll 1
-    for (u32 j = 0; j < w; j++) {
-        u32 s[8];
-        load8(scalars, (u64)r * w + j, s);
-        if (rows_recode(s)) flags[ROWS_FLAG_BIT255] = 1u;
-        u32 mine = s[0];
-        for (u32 q = 1; q < 8; q++) mine = word == q ? s[q] : mine;
-        const int dg = rows_digit((mine >> shift) & 15u, (int)lane);
-        if (dg != 0) {
-            const bool neg = dg < 0;
-            const u32 mag = (u32)(neg ? -dg : dg);                          // 1 .. 8
-            acc = ge_madd_signed_p3(acc, pts_load(tab, ((u64)j * ROWS_WIN + lane) * ROWS_ENT + ((mag - 1u) & 7u)), neg);
-        }
-        ge_pin(acc);
-    }
-#pragma unroll 1
-    for (int off = 32; off > 0; off >>= 1) acc = ge_add(acc, ge_shfl_down(acc, off));
+    straus_comb_wave(acc, scalars, (u64)r * w, w, tab, lane, flags);
+    acc = straus_wave_fold(acc);
     if (lane == 0) raw160_store(out_raw, r, acc);
 }
 
 }  // namespace c25519
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-static inline size_t rows_al256(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr uint64_t ROWS_BUILD_CHUNK = 256;                  // static points per build step: 256 x 512 raw points = 20 MB of scratch
-
-// (ctx may be null: c25519_precomp_msm_vartime_rows_plan has none, and then only the code is returned)
-static int32_t rows_bad(c25519_ctx *ctx, const char *what) { return ctx ? bad_arg(ctx, what) : -(int32_t)hipErrorInvalidValue; }
 
 // ---- routing: the one place that chooses the kernel of a call ----
 static int32_t rows_plan(c25519_ctx *ctx, uint64_t m, uint64_t w, uint64_t plan[2]) {
-    if (m >= 0xffffffffull) return rows_bad(ctx, "precomp_msm_vartime_rows: m must be below 2^32 - 1");
-    if (w && m > UINT64_MAX / w) return rows_bad(ctx, "precomp_msm_vartime_rows: m * w overflows");
-    const bool lane = w < C25519_PRECOMP_ROWS_LANE_WIDTH && m >= C25519_PRECOMP_ROWS_LANE_MIN_ROWS;
+    if (m >= 0xffffffffull) return bad_arg(ctx, "precomp_msm_vartime_rows: m must be below 2^32 - 1");
+    if (w && m > UINT64_MAX / w) return bad_arg(ctx, "precomp_msm_vartime_rows: m * w overflows");
+    const bool lane = rows_lane_route(m, w);
     plan[0] = lane ? C25519_PRECOMP_ROWS_LANE : C25519_PRECOMP_ROWS_WAVE;
     plan[1] = lane ? (m + 63) / 64 : m;
     return C25519_OK;
@@ -153,16 +104,10 @@ EXPORT uint64_t c25519_precomp_rows_table_bytes(const c25519_precomp *p) { retur
 
 // everything that is refused before any launch; route_out: the kernel of this call
 static int32_t rows_check(c25519_ctx *ctx, const c25519_precomp *p, uint64_t m, uint64_t w, int32_t route, int out_fmt, int32_t &route_out) {
-    if (!p) return bad_arg(ctx, "precomp_msm_vartime_rows: no handle");
-    if (out_fmt < 0 || out_fmt > 2) return bad_arg(ctx, "precomp_msm_vartime_rows: bad out_fmt");
-    if (route != C25519_PRECOMP_ROWS_AUTO && route != C25519_PRECOMP_ROWS_LANE && route != C25519_PRECOMP_ROWS_WAVE)
-        return bad_arg(ctx, "precomp_msm_vartime_rows: unknown route");
-    if (p->n > C25519_PRECOMP_ROWS_MAX_POINTS)
-        return bad_arg(ctx, "precomp_msm_vartime_rows: the handle has more than 4096 static points; run it through c25519_precomp_msm_vartime, row by row");
-    if (w > p->n) return bad_arg(ctx, "precomp_msm_vartime_rows: more scalars per row than static points (precomputed_straus.rs:86)");
+    static const rows_msgs msgs = ROWS_MSGS("precomp_msm_vartime_rows", "scalars");
     uint64_t plan[2];
-    const int32_t r = rows_plan(ctx, m, w, plan);
-    if (r) return r;
+    int32_t r;
+    if ((r = rows_check_handle(ctx, msgs, p, w, route, out_fmt)) || (r = rows_plan(ctx, m, w, plan))) return r;
     route_out = route == C25519_PRECOMP_ROWS_AUTO ? (int32_t)plan[0] : route;
     return C25519_OK;
 }
@@ -193,15 +138,13 @@ int32_t rows_build(c25519_ctx *ctx, c25519_precomp *p) {
 // copied before the one synchronisation.
 static int32_t rows_run(c25519_ctx *ctx, c25519_precomp *p, const uint8_t *d_scalars, uint64_t m, uint64_t w, int32_t route, int out_fmt, uint8_t *d_out, uint8_t *h_out) {
     hipStream_t st = ctx->stream;
-    const size_t ob = point_bytes(out_fmt);
     uint32_t *flags = (uint32_t *)ctx->d_flag;
-    uint32_t *verdict = (uint32_t *)ctx->h_msm;           // pinned
     auto enqueue = [&]() -> int32_t {
         int32_t r;
         HIPCHK(hipEventRecord(ctx->ev0, st));
         // tmp_f: the raw sums (compressed output only); a first call's build has its scratch there before them, in stream order (reserved in this
         // order, so the buffer never moves under queued work)
-        if (out_fmt != C25519_FMT_RAW160 && (r = ctx_reserve(ctx, ctx->tmp_f, rows_al256(m * 160) + 256))) return r;
+        if (out_fmt != C25519_FMT_RAW160 && (r = ctx_reserve(ctx, ctx->tmp_f, al256(m * 160) + 256))) return r;
         if ((r = rows_build(ctx, p))) return r;
         uint8_t *sums = out_fmt == C25519_FMT_RAW160 ? d_out : (uint8_t *)ctx->tmp_f.p;
         HIPCHK(hipMemsetAsync(flags, 0, 8, st));
@@ -213,17 +156,9 @@ static int32_t rows_run(c25519_ctx *ctx, c25519_precomp *p, const uint8_t *d_sca
             hipLaunchKernelGGL(k_mid_rows_wave, dim3(div_up(m, 4)), dim3(256), 0, st, d_scalars, (u32)m, (u32)w, (const u32 *)p->d_rows, sums, flags);
         }
         HIPCHK(hipGetLastError());
-        if (out_fmt != C25519_FMT_RAW160 && (r = c25519_compress_batch_dev(ctx, sums, m, out_fmt, d_out))) return r;
-        HIPCHK(hipEventRecord(ctx->ev1, st));
-        HIPCHK(hipMemcpyAsync(verdict, flags, 8, hipMemcpyDeviceToHost, st));
-        if (h_out) HIPCHK(hipMemcpyAsync(h_out, d_out, m * ob, hipMemcpyDeviceToHost, st));
-        return C25519_OK;
+        return straus_finish_enqueue(ctx, sums, m, out_fmt, d_out, nullptr, h_out, nullptr);
     };
-    const int32_t r = enqueue();
-    if (r) { (void)hipStreamSynchronize(st); return r; }   // no queued copy still reads host memory after the return
-    HIPCHK(hipStreamSynchronize(st));
-    if (verdict[ROWS_FLAG_BIT255]) return bad_arg(ctx, "msm: a scalar has bit 255 set (Scalar invariant #1 violated)");
-    return C25519_OK;
+    return straus_finish_wait(ctx, enqueue(), false);      // (no kernel of this call raises the NONE word: the handle's points were decoded at its creation)
 }
 
 EXPORT int32_t c25519_precomp_msm_vartime_rows_dev(c25519_ctx *ctx, c25519_precomp *p, const uint8_t *d_scalars, uint64_t m, uint64_t w, int32_t route, int out_fmt,
@@ -245,10 +180,7 @@ EXPORT int32_t c25519_precomp_msm_vartime_rows(c25519_ctx *ctx, c25519_precomp *
     if ((r = ctx_reserve(ctx, ctx->tmp_a, sb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, m * ob + 16))) return r;
     ffi_small_begin(ctx);
     uint8_t *d_s = (uint8_t *)ctx->tmp_a.p, *d_out = (uint8_t *)ctx->tmp_c.p;
-    if (sb) {
-        const hipError_t e = hipMemcpyAsync(d_s, scalars, sb, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return c25519_fail(ctx, e, "hipMemcpyAsync(inputs)"); }
-    }
+    if ((r = straus_upload_all(ctx, {{d_s, scalars, sb}}))) return r;
     r = rows_run(ctx, p, d_s, m, w, kernel, out_fmt, d_out, out);
     ffi_small_end(ctx, sb, m * ob);
     return r;

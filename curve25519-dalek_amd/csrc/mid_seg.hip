@@ -5,15 +5,15 @@
 //   c25519_msm_vartime_segments_dev / c25519_msm_vartime_segments / c25519_msm_vartime_segments_plan
 //
 // Straus with the doubling chain shared by the terms of a segment (scalar_mul/straus.rs:159-200), one LANE per segment:
-//   (the table layout, the body of the tables kernel and the three constants live in seg_tables.h, shared with mid_mixed.hip)
-//   k_mid_seg_tables   one lane per term: decodes the point, writes its ok byte, the table {1 .. 8} P as eight 160-byte ProjectiveNiels
+//   (the table layout, the tables kernel, the window loops and the three constants live in straus.h, shared with mid_mixed.hip)
+//   k_mid_straus_tables   one lane per term: decodes the point, writes its ok byte, the table {1 .. 8} P as eight 160-byte ProjectiveNiels
 //                      records (Y+X, Y-X, Z, 2dT) and the 64 signed radix-16 digits of the scalar (scalar.rs:1019-1051), raises the bit-255 flag
-//   k_mid_seg_straus   one lane per segment of at most C25519_MSM_SEGMENT_DIRECT_MAX terms: acc = 16 acc per window, then + / - entry |d| of
-//                      every term whose digit d is not zero.  Complete formulas (edwards.rs:797): no special case for equal, opposite or
-//                      identity operands.  The sum leaves as a raw 160-byte point.
-//   k_mid_seg_wave     one WAVE per segment of at most C25519_MSM_SEGMENT_WAVE_MAX terms: lane l takes terms l, l + 64, l + 128, ... and runs
-//                      the same window loop over them; the 64 partial sums are folded across the wave with six shuffle rounds.  (The constant
-//                      is measured; the kernel itself is correct for any length.)
+//   k_mid_seg_straus   one lane per segment of at most C25519_MSM_SEGMENT_DIRECT_MAX terms (straus_dyn_lane): acc = 16 acc per window, then
+//                      + / - entry |d| of every term whose digit d is not zero.  Complete formulas (edwards.rs:797): no special case for equal,
+//                      opposite or identity operands.  The sum leaves as a raw 160-byte point.
+//   k_mid_seg_wave     one WAVE per segment of at most C25519_MSM_SEGMENT_WAVE_MAX terms (the loop of straus_dyn_wave): lane l takes terms l, l + 64,
+//                      l + 128, ... and runs the same window loop over them; the 64 partial sums are folded across the wave with six shuffle
+//                      rounds.  (The constant is measured; the kernel itself is correct for any length.)
 // Compressed outputs go through c25519_compress_batch_dev (no second inversion here).  Segments longer than the wave maximum run through
 // c25519_msm_partial_dev, one call each, and their sums are placed beside the others before that finishing step.
 // The scalars are public by contract (a *_vartime entry point): branches and table addresses depend on their digits.  Every loop bound comes
@@ -22,28 +22,17 @@
 #include <algorithm>
 #include <string.h>
 #include <vector>
-#include "../../include/c25519_hip.h"
-#include "devio.h"
-#include "kernels.h"
-#include "ctx.h"
+#include "straus.h"                         // (and through it devio.h, kernels.h, ctx.h, knobs.h, precomp.h, rows_digits.h, capi_util.h)
 #include "ffi.h"
-#include "knobs.h"
-#include "capi_util.h"
-#include "seg_tables.h"
 
 using namespace c25519;
 
 namespace c25519 {
 
-// Terms [t0, t0 + cnt) of the call -> records 0 .. cnt - 1 of the pass: tok[i], tab[i], dig[i].  IN: 0 CompressedEdwardsY (ZIP-215 decoder),
-// 1 CompressedRistretto, 2 raw 160-byte (trusted).  The body is seg_tables.h seg_tables_term (shared with mid_mixed.hip).
-template <int IN>
-__global__ void __launch_bounds__(256) k_mid_seg_tables(const uint8_t *__restrict__ scalars, const uint8_t *__restrict__ points, u64 t0, u64 cnt,
-                                                        uint4 *__restrict__ tab, uint4 *__restrict__ dig, uint8_t *__restrict__ tok, u32 *__restrict__ flags) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= cnt) return;
-    seg_tables_term<IN>(scalars, points, t0 + i, i, tab, dig, tok, flags);
-}
+// the library's one copy of the tables kernel (straus.h declares the three extern)
+template __global__ void k_mid_straus_tables<0>(const uint8_t *, const uint8_t *, u64, u64, uint4 *, uint4 *, uint8_t *, u32 *);
+template __global__ void k_mid_straus_tables<1>(const uint8_t *, const uint8_t *, u64, u64, uint4 *, uint4 *, uint8_t *, u32 *);
+template __global__ void k_mid_straus_tables<2>(const uint8_t *, const uint8_t *, u64, u64, uint4 *, uint4 *, uint8_t *, u32 *);
 
 // Segments [s0, s0 + cnt) of the call, whose terms are records [seg_off[s] - t0, seg_off[s + 1] - t0) of the pass (nt records).  A segment
 // that is longer than dmax or does not lie within the records is left alone (the longer ones of a pass belong to k_mid_seg_wave).
@@ -57,33 +46,18 @@ __global__ void __launch_bounds__(256) k_mid_seg_straus(const u64 *__restrict__ 
     const u64 lo = a - t0;
     const u32 len = (u32)(b - a);
     u32 good = 1;
-    for (u32 j = 0; j < len; j++) good &= (u32)tok[lo + j];
     ge_p3 acc = ge_identity();
-#pragma unroll 1
-    for (int w = SEG_DIG - 1; w >= 0; w--) {
-        if (w != SEG_DIG - 1) acc = ge_mul_by_pow_2(acc, 4);
-#pragma unroll 1
-        for (u32 j = 0; j < len; j++) {
-            const int dg = (int)dig[(lo + j) * SEG_DIG + (u64)w];
-            if (dg != 0) {
-                const bool neg = dg < 0;
-                const u32 mag = (u32)(neg ? -dg : dg);                      // 1 .. 8
-                const ge_cached c = seg_tab_load(tab, lo + j, (mag - 1u) & 7u);
-                acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_cached_cneg(c, neg)));
-            }
-        }
-        ge_pin(acc);
-    }
+    straus_dyn_lane(acc, good, tab, dig, tok, lo, len);
     raw160_store(out_raw, s, acc);
     ok[s] = (uint8_t)good;
     if (!good) flags[SEG_FLAG_NONE] = 1u;
 }
 
 // Wave w of the launch takes segment ids[w] (cnt ids: the pass's segments of more than dmax terms), whose terms are records
-// [seg_off[s] - t0, seg_off[s + 1] - t0) of the pass, as for k_mid_seg_straus.  Lane l handles terms l, l + 64, ... of the segment: the window
-// loop of k_mid_seg_straus over its own terms, then the 64 partial sums are folded (ge_shfl_down, complete additions: a lane without a term
-// holds the identity) and lane 0 stores the sum and the verdict.  Correct for any length >= 1.  The segment index, the offsets and every loop
-// bound are wave-uniform (readfirstlane: SGPRs); only the term predicate and the zero-digit skip depend on the lane.  No LDS, no barrier.
+// [seg_off[s] - t0, seg_off[s + 1] - t0) of the pass, as for k_mid_seg_straus.  Lane l handles terms l, l + 64, ... of the segment
+// (the window loop of straus_dyn_wave), then the 64 partial sums are folded and lane 0 stores the sum and the verdict.  Correct for any length >= 1.  The
+// segment index, the offsets and every loop bound are wave-uniform (readfirstlane: SGPRs); only the term predicate and the zero-digit skip
+// depend on the lane.  No LDS, no barrier.
 __global__ void __launch_bounds__(256) k_mid_seg_wave(const u64 *__restrict__ seg_off, const u32 *__restrict__ ids, u32 cnt, u64 t0, u64 nt, const uint4 *__restrict__ tab,
                                                       const int8_t *__restrict__ dig, const uint8_t *__restrict__ tok, uint8_t *__restrict__ out_raw,
                                                       uint8_t *__restrict__ ok, u32 *__restrict__ flags) {
@@ -95,6 +69,8 @@ __global__ void __launch_bounds__(256) k_mid_seg_wave(const u64 *__restrict__ se
     if (a < t0 || b < a || b - t0 > nt || b - a > 0xffffffc0ull) return;
     const u64 lo = a - t0;
     const u32 len = (u32)(b - a), rounds = (len + 63u) >> 6;
+    // The loop of straus_dyn_wave, written out: called as that function the kernel is allocated 147 VGPRs where this form gets 128, one wave
+    // per SIMD fewer (the same instructions; measured on the compiled code, profiles/straus_family_isa.txt).  A change there belongs here too.
     u32 good = 1;
     for (u32 r = 0; r < rounds; r++) {
         const u32 j = 64u * r + lane;
@@ -109,46 +85,21 @@ __global__ void __launch_bounds__(256) k_mid_seg_wave(const u64 *__restrict__ se
             const u32 j = 64u * r + lane;
             if (j < len) {
                 const int dg = (int)dig[(lo + j) * SEG_DIG + (u64)w];
-                if (dg != 0) {
-                    const bool neg = dg < 0;
-                    const u32 mag = (u32)(neg ? -dg : dg);                  // 1 .. 8
-                    const ge_cached c = seg_tab_load(tab, lo + j, (mag - 1u) & 7u);
-                    acc = ge_p1p1_to_p3(ge_add_cached(acc, ge_cached_cneg(c, neg)));
-                }
+                if (dg != 0) acc = straus_add_dyn(acc, tab, lo + j, dg);
             }
         }
         ge_pin(acc);
     }
-#pragma unroll 1
-    for (int off = 32; off > 0; off >>= 1) acc = ge_add(acc, ge_shfl_down(acc, off));
-    const bool all_good = __all((int)good) != 0;
-    if (lane == 0) {
-        raw160_store(out_raw, s, acc);
-        ok[s] = all_good ? 1 : 0;
-        if (!all_good) flags[SEG_FLAG_NONE] = 1u;
-    }
+    straus_wave_store(out_raw, ok, flags, s, straus_wave_fold(acc), good, lane);
 }
 
 }  // namespace c25519
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-// (ctx may be null: c25519_msm_vartime_segments_plan has none, and then only the code is returned)
-static int32_t seg_bad(c25519_ctx *ctx, const char *what) { return ctx ? bad_arg(ctx, what) : -(int32_t)hipErrorInvalidValue; }
-static int32_t seg_check_off(c25519_ctx *ctx, uint64_t n, const uint64_t *seg_off, uint64_t m) {
-    if (m >= 0xffffffffull) return seg_bad(ctx, "msm_vartime_segments: m must be below 2^32 - 1");
-    if (n >= (1ull << 40)) return seg_bad(ctx, "msm_vartime_segments: n must be < 2^40");
-    if (m == 0) return C25519_OK;
-    if (!seg_off || seg_off[0] != 0 || seg_off[m] != n) return seg_bad(ctx, "msm_vartime_segments: seg_off must run from 0 to n");
-    for (uint64_t s = 0; s < m; s++)
-        if (seg_off[s + 1] < seg_off[s]) return seg_bad(ctx, "msm_vartime_segments: seg_off must be non-decreasing");
-    return C25519_OK;
-}
+static const off_msgs SEG_OFF_MSGS = OFF_MSGS("msm_vartime_segments", "seg_off", "n", nullptr);
 static int32_t seg_check(c25519_ctx *ctx, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m, int out_fmt) {
-    const bool pair = in_fmt == C25519_FMT_EDWARDS_Y ? ed_fmt_ok(out_fmt)
-                    : in_fmt == C25519_FMT_RISTRETTO ? ris_fmt_ok(out_fmt)
-                    : in_fmt == C25519_FMT_RAW160 && (ed_fmt_ok(out_fmt) || out_fmt == C25519_FMT_RISTRETTO);
-    if (!pair) return bad_arg(ctx, "msm_vartime_segments: in_fmt and out_fmt must belong to one group");
-    return seg_check_off(ctx, n, seg_off, m);
+    if (!fmt_pair_ok(in_fmt, out_fmt)) return bad_arg(ctx, "msm_vartime_segments: in_fmt and out_fmt must belong to one group");
+    return check_offsets(ctx, SEG_OFF_MSGS, n, seg_off, m);
 }
 
 // ---- routing: the one place that decides which kernel a segment gets and where the passes are cut ----
@@ -179,16 +130,15 @@ static void seg_plan(const uint64_t *seg_off, uint64_t m, bool lists, seg_route 
         if (len > wmax) { close(s); s0 = s + 1; R.n_long++; if (lists) R.longs.push_back(s); continue; }
         if (terms + len > ptmax) { close(s); s0 = s; }
         terms += len;
-        if (len > dmax) { R.n_wave++; if (lists) R.wave_ids.push_back((uint32_t)s); }     // s < m < 2^32 - 1: seg_check_off has bounded m
+        if (len > dmax) { R.n_wave++; if (lists) R.wave_ids.push_back((uint32_t)s); }     // s < m < 2^32 - 1: check_offsets has bounded m
         else { R.n_lane++; lanes++; }
     }
     close(m);
 }
 
 EXPORT int32_t c25519_msm_vartime_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[5]) {
-    if (m >= 0xffffffffull) return seg_bad(nullptr, "m");    // before seg_off[m] is read for n
     int32_t r;
-    if ((r = seg_check_off(nullptr, (m && seg_off) ? seg_off[m] : 0, seg_off, m))) return r;
+    if ((r = check_offsets(nullptr, SEG_OFF_MSGS, offsets_end(seg_off, m), seg_off, m))) return r;
     seg_route R;
     seg_plan(seg_off, m, false, R);
     plan[0] = R.n_lane; plan[1] = R.n_wave; plan[2] = R.n_long; plan[3] = R.n_pass; plan[4] = R.maxt;
@@ -200,7 +150,7 @@ EXPORT int32_t c25519_msm_vartime_segments_plan(const uint64_t *seg_off, uint64_
 static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m, int out_fmt,
                        uint8_t *d_out, uint8_t *d_ok, uint8_t *h_out, uint8_t *h_ok) {
     hipStream_t st = ctx->stream;
-    const size_t pb = point_bytes(in_fmt), ob = point_bytes(out_fmt);
+    const size_t pb = point_bytes(in_fmt);
     const uint64_t dmax = seg_direct_max();
     seg_route R;
     seg_plan(seg_off, m, true, R);
@@ -219,68 +169,42 @@ static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
             long_sum[160 * k + 40] = 1; long_sum[160 * k + 80] = 1;
         } else if (r) return r;
     }
-    // tmp_f: seg_off | segment ids of the wave route, pass after pass | raw sums (compressed output only) | ok (without d_ok) | tables | digits |
-    // term ok bytes
-    const size_t b_off = seg_al256((m + 1) * 8) + seg_al256(R.wave_ids.size() * 4), b_sum = out_fmt == C25519_FMT_RAW160 ? 0 : seg_al256(m * 160), b_ok = d_ok ? 0 : seg_al256(m);
-    const size_t b_tab = seg_al256(maxt * SEG_ENT * SEG_ENT_Q * 16), b_dig = seg_al256(maxt * SEG_DIG), b_tok = seg_al256(maxt);
+    // tmp_f (straus_ws): seg_off | segment ids of the wave route, pass after pass | raw sums | ok | tables | digits | term ok bytes
+    straus_ws ws(m, R.wave_ids.size(), maxt, out_fmt, d_ok != nullptr);
     int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, b_off + b_sum + b_ok + b_tab + b_dig + b_tok + 256))) return r;
-    uint8_t *base = (uint8_t *)ctx->tmp_f.p;
-    uint64_t *d_off = (uint64_t *)base;
-    uint32_t *d_ids = (uint32_t *)(base + seg_al256((m + 1) * 8));
-    uint8_t *sums = out_fmt == C25519_FMT_RAW160 ? d_out : base + b_off;
-    uint8_t *okbuf = d_ok ? d_ok : base + b_off + b_sum;
-    uint4 *tab = (uint4 *)(base + b_off + b_sum + b_ok);
-    uint8_t *dig = base + b_off + b_sum + b_ok + b_tab, *tok = dig + b_dig;
+    if ((r = ctx_reserve(ctx, ctx->tmp_f, ws.bytes()))) return r;
+    ws.carve((uint8_t *)ctx->tmp_f.p, d_out, d_ok);
     uint32_t *flags = (uint32_t *)ctx->d_flag;
-    uint32_t *verdict = (uint32_t *)ctx->h_msm;           // pinned
     auto enqueue = [&]() -> int32_t {
         HIPCHK(hipMemsetAsync(flags, 0, 8, st));
         HIPCHK(hipEventRecord(ctx->ev0, st));
-        HIPCHK(hipMemcpyAsync(d_off, seg_off, (m + 1) * 8, hipMemcpyHostToDevice, st));
-        if (!R.wave_ids.empty()) HIPCHK(hipMemcpyAsync(d_ids, R.wave_ids.data(), R.wave_ids.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ws.d_off, seg_off, (m + 1) * 8, hipMemcpyHostToDevice, st));
+        if (!R.wave_ids.empty()) HIPCHK(hipMemcpyAsync(ws.d_ids, R.wave_ids.data(), R.wave_ids.size() * 4, hipMemcpyHostToDevice, st));
         ctx->kname[0] = R.wave_ids.empty() ? "c25519::k_mid_seg_straus (one lane per segment, the doubling chain shared by its terms)"
                                            : "c25519::k_mid_seg_wave (one wave per segment, lane l takes terms l, l + 64, ...; the partial sums folded by shuffles)";
         for (const seg_pass &p : passes) {
             const uint64_t t0 = seg_off[p.s0], nt = seg_off[p.s1] - t0, ns = p.s1 - p.s0;
-            if (nt) {
-                const dim3 g(div_up(nt, 256)), b(256);
-                if (in_fmt == C25519_FMT_EDWARDS_Y) hipLaunchKernelGGL(k_mid_seg_tables<0>, g, b, 0, st, d_scalars, d_points, t0, nt, tab, (uint4 *)dig, tok, flags);
-                else if (in_fmt == C25519_FMT_RISTRETTO) hipLaunchKernelGGL(k_mid_seg_tables<1>, g, b, 0, st, d_scalars, d_points, t0, nt, tab, (uint4 *)dig, tok, flags);
-                else hipLaunchKernelGGL(k_mid_seg_tables<2>, g, b, 0, st, d_scalars, d_points, t0, nt, tab, (uint4 *)dig, tok, flags);
-                HIPCHK(hipGetLastError());
-            }
+            int32_t q;
+            if (nt && (q = straus_launch_tables(ctx, in_fmt, d_scalars, d_points, t0, nt, ws))) return q;
             if (p.lanes) {                                   // (the wave segments among its lanes are longer than dmax: left alone)
-                hipLaunchKernelGGL(k_mid_seg_straus, dim3(div_up(ns, 256)), dim3(256), 0, st, (const u64 *)d_off, p.s0, ns, t0, nt, (u32)dmax, (const uint4 *)tab,
-                                   (const int8_t *)dig, (const uint8_t *)tok, sums, okbuf, flags);
+                hipLaunchKernelGGL(k_mid_seg_straus, dim3(div_up(ns, 256)), dim3(256), 0, st, (const u64 *)ws.d_off, p.s0, ns, t0, nt, (u32)dmax, (const uint4 *)ws.tab,
+                                   (const int8_t *)ws.dig, (const uint8_t *)ws.tok, ws.sums, ws.okbuf, flags);
                 HIPCHK(hipGetLastError());
             }
             if (p.w1 > p.w0) {                               // four waves, so four segments, per block; disjoint outputs: back to back on the stream
                 const uint64_t nw = p.w1 - p.w0;
-                hipLaunchKernelGGL(k_mid_seg_wave, dim3(div_up(nw, 4)), dim3(256), 0, st, (const u64 *)d_off, (const u32 *)(d_ids + p.w0), (u32)nw, t0, nt,
-                                   (const uint4 *)tab, (const int8_t *)dig, (const uint8_t *)tok, sums, okbuf, flags);
+                hipLaunchKernelGGL(k_mid_seg_wave, dim3(div_up(nw, 4)), dim3(256), 0, st, (const u64 *)ws.d_off, (const u32 *)(ws.d_ids + p.w0), (u32)nw, t0, nt,
+                                   (const uint4 *)ws.tab, (const int8_t *)ws.dig, (const uint8_t *)ws.tok, ws.sums, ws.okbuf, flags);
                 HIPCHK(hipGetLastError());
             }
         }
         for (size_t k = 0; k < longs.size(); k++) {
-            HIPCHK(hipMemcpyAsync(sums + longs[k] * 160, long_sum.data() + 160 * k, 160, hipMemcpyHostToDevice, st));
-            HIPCHK(hipMemcpyAsync(okbuf + longs[k], long_ok.data() + k, 1, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ws.sums + longs[k] * 160, long_sum.data() + 160 * k, 160, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ws.okbuf + longs[k], long_ok.data() + k, 1, hipMemcpyHostToDevice, st));
         }
-        if (out_fmt != C25519_FMT_RAW160) {
-            const int32_t q = c25519_compress_batch_dev(ctx, sums, m, out_fmt, d_out);
-            if (q) return q;
-        }
-        HIPCHK(hipEventRecord(ctx->ev1, st));
-        HIPCHK(hipMemcpyAsync(verdict, flags, 8, hipMemcpyDeviceToHost, st));
-        if (h_out) HIPCHK(hipMemcpyAsync(h_out, d_out, m * ob, hipMemcpyDeviceToHost, st));
-        if (h_ok) HIPCHK(hipMemcpyAsync(h_ok, okbuf, m, hipMemcpyDeviceToHost, st));
-        return C25519_OK;
+        return straus_finish_enqueue(ctx, ws.sums, m, out_fmt, d_out, ws.okbuf, h_out, h_ok);
     };
-    r = enqueue();
-    if (r) { (void)hipStreamSynchronize(st); return r; }   // no queued copy still reads host memory after the return
-    HIPCHK(hipStreamSynchronize(st));
-    if (verdict[SEG_FLAG_BIT255]) return bad_arg(ctx, "msm: a scalar has bit 255 set (Scalar invariant #1 violated)");
-    return (verdict[SEG_FLAG_NONE] || long_none) ? C25519_NONE : C25519_OK;
+    return straus_finish_wait(ctx, enqueue(), long_none);
 }
 
 EXPORT int32_t c25519_msm_vartime_segments_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt, const uint64_t *seg_off,
@@ -299,15 +223,11 @@ EXPORT int32_t c25519_msm_vartime_segments(c25519_ctx *ctx, const uint8_t *scala
     if ((r = seg_check(ctx, n, in_fmt, seg_off, m, out_fmt))) return r;
     if (m == 0) return C25519_OK;
     const size_t pb = point_bytes(in_fmt), ob = point_bytes(out_fmt);
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * pb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, seg_al256(m * ob) + m + 16)))
+    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * pb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, al256(m * ob) + m + 16)))
         return r;
     ffi_small_begin(ctx);
-    uint8_t *d_s = (uint8_t *)ctx->tmp_a.p, *d_p = (uint8_t *)ctx->tmp_b.p, *d_out = (uint8_t *)ctx->tmp_c.p, *d_ok = d_out + seg_al256(m * ob);
-    if (n) {
-        hipError_t e = hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_p, points, n * pb, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return c25519_fail(ctx, e, "hipMemcpyAsync(inputs)"); }
-    }
+    uint8_t *d_s = (uint8_t *)ctx->tmp_a.p, *d_p = (uint8_t *)ctx->tmp_b.p, *d_out = (uint8_t *)ctx->tmp_c.p, *d_ok = d_out + al256(m * ob);
+    if ((r = straus_upload_all(ctx, {{d_s, scalars, n * 32}, {d_p, points, n * pb}}))) return r;
     r = seg_run(ctx, d_s, d_p, n, in_fmt, seg_off, m, out_fmt, d_out, d_ok, out, ok);
     if (r < 0) (void)hipStreamSynchronize(ctx->stream);    // (an early error: the uploads may still be reading the caller's memory)
     ffi_small_end(ctx, n * (32 + pb) + (m + 1) * 8, m * ob + (ok ? m : 0));

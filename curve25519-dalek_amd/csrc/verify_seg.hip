@@ -267,24 +267,14 @@ __global__ void __launch_bounds__(256) k_mid_vseg_verdict(const uint8_t *__restr
 }  // namespace c25519
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-static inline size_t vseg_al256(size_t b) { return (b + 255) & ~(size_t)255; }
 static uint64_t vseg_pass_terms() {                         // (tuning build: other pass sizes for an A/B run; at least one longest segment)
     static const uint64_t v = std::max<uint64_t>((uint64_t)std::max<long long>(1, C25519_KNOB_LL("VSEG_PASS_TERMS", C25519_MSM_SEGMENT_PASS_TERMS)),
                                                  2 * (uint64_t)ED25519_VERIFY_SEGMENT_MAX + 1);
     return v;
 }
-// (ctx may be null: ed25519_verify_batch_segments_plan has none)
-static int32_t vseg_bad(c25519_ctx *ctx, const char *what) { return ctx ? bad_arg(ctx, what) : -(int32_t)hipErrorInvalidValue; }
-// the checks of c25519_msm_vartime_segments on its offsets
-static int32_t vseg_check_off(c25519_ctx *ctx, uint64_t n, const uint64_t *seg_off, uint64_t m) {
-    if (m >= 0xffffffffull) return vseg_bad(ctx, "verify_batch_segments: m must be below 2^32 - 1");
-    if (n >= (1ull << 40)) return vseg_bad(ctx, "verify_batch_segments: n must be < 2^40");
-    if (m == 0) return C25519_OK;
-    if (!seg_off || seg_off[0] != 0 || seg_off[m] != n) return vseg_bad(ctx, "verify_batch_segments: seg_off must run from 0 to n");
-    for (uint64_t s = 0; s < m; s++)
-        if (seg_off[s + 1] < seg_off[s]) return vseg_bad(ctx, "verify_batch_segments: seg_off must be non-decreasing");
-    return C25519_OK;
-}
+// the checks of c25519_msm_vartime_segments on its offsets (ctx may be null: the *_plan exports have none)
+static const off_msgs VSEG_OFF_MSGS = OFF_MSGS("verify_batch_segments", "seg_off", "n", nullptr);
+static int32_t vseg_check_off(c25519_ctx *ctx, uint64_t n, const uint64_t *seg_off, uint64_t m) { return check_offsets(ctx, VSEG_OFF_MSGS, n, seg_off, m); }
 
 // ---- the transcripts of the segments ----
 // The longest segment whose transcript ed25519_verify_batch_segments runs on the device (longer ones of the segmented route: the host sponge).
@@ -305,9 +295,8 @@ static hipError_t vseg_launch_transcript(c25519_ctx *ctx, const uint64_t *d_off,
 }
 
 EXPORT int32_t ed25519_batch_transcript_zs_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[2]) {
-    if (m >= 0xffffffffull) return vseg_bad(nullptr, "m");   // before seg_off[m] is read for n
     int32_t r;
-    if ((r = vseg_check_off(nullptr, (m && seg_off) ? seg_off[m] : 0, seg_off, m))) return r;
+    if ((r = vseg_check_off(nullptr, offsets_end(seg_off, m), seg_off, m))) return r;
     plan[0] = plan[1] = 0;
     for (uint64_t s = 0; s < m; s++) {
         const uint64_t len = seg_off[s + 1] - seg_off[s];
@@ -387,9 +376,8 @@ static void vseg_plan(const uint64_t *seg_off, uint64_t m, bool lists, vseg_rout
 }
 
 EXPORT int32_t ed25519_verify_batch_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[4]) {
-    if (m >= 0xffffffffull) return vseg_bad(nullptr, "m");   // before seg_off[m] is read for n
     int32_t r;
-    if ((r = vseg_check_off(nullptr, (m && seg_off) ? seg_off[m] : 0, seg_off, m))) return r;
+    if ((r = vseg_check_off(nullptr, offsets_end(seg_off, m), seg_off, m))) return r;
     vseg_route R;
     vseg_plan(seg_off, m, false, R);
     plan[0] = R.n_seg; plan[1] = R.n_long; plan[2] = R.n_pass; plan[3] = R.maxt;
@@ -445,10 +433,10 @@ static int32_t vseg_run(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *
             }
     // tmp_c2 (the call): hram | its two counters | z16 | seg_off | tree states | statuses (host form)
     // tmp_d (sized by the largest pass): term scalars | term points | sums | z s | flags of R, of A, of the segments
-    const size_t c_h = vseg_al256(n * 64), c_fl = 256, c_z = vseg_al256((n + 4) * 16), c_off = vseg_al256((m + 1) * 8), c_slot = vseg_al256(iv_slot.size() * 2),
-                 c_iv = vseg_al256(ivs.size() * 8), c_st = d_status ? 0 : vseg_al256(m);
-    const size_t p_sc = vseg_al256(R.maxt * 32), p_pt = vseg_al256(R.maxt * 160), p_sum = vseg_al256(R.max_segs * 160), p_zs = vseg_al256(R.max_sigs * 40),
-                 p_f = vseg_al256(R.max_sigs), p_sf = vseg_al256(R.max_segs);
+    const size_t c_h = al256(n * 64), c_fl = 256, c_z = al256((n + 4) * 16), c_off = al256((m + 1) * 8), c_slot = al256(iv_slot.size() * 2),
+                 c_iv = al256(ivs.size() * 8), c_st = d_status ? 0 : al256(m);
+    const size_t p_sc = al256(R.maxt * 32), p_pt = al256(R.maxt * 160), p_sum = al256(R.max_segs * 160), p_zs = al256(R.max_sigs * 40),
+                 p_f = al256(R.max_sigs), p_sf = al256(R.max_segs);
     if ((r = ctx_reserve(ctx, ctx->tmp_c2, c_h + c_fl + c_z + c_off + c_slot + c_iv + c_st + 256)) ||
         (r = ctx_reserve(ctx, ctx->tmp_d, p_sc + p_pt + p_sum + p_zs + 2 * p_f + p_sf + 256)))
         return r;

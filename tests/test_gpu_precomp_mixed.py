@@ -1,5 +1,5 @@
 """Many mixed multiscalar muls over one precomputed point set on the GPU (csrc/mid_mixed.hip: c25519_precomp_msm_vartime_mixed_rows,
-k_mid_mixed_tables, k_mid_mixed_lane, k_mid_mixed_wave).  Every expected value is eng.precomp_msm_vartime on that row alone (byte equality in
+k_mid_straus_tables, k_mid_mixed_lane, k_mid_mixed_wave).  Every expected value is eng.precomp_msm_vartime on that row alone (byte equality in
 formats 0 and 1; RAW160 outputs after compress_batch); the cancellation cases are checked against the CPU oracle's MSM, two shapes against the
 three-call composition rows -> segments -> point_add_batch.  The static points, the scalar matrix and the SPECIAL scalars are those of
 test_gpu_precomp_rows.py.  All three routes (LANE, WAVE, AUTO) run on every shape and must agree."""
@@ -329,6 +329,50 @@ def test_table_is_shared_with_the_rows_call(eng, orc, golden):
         assert st == 0 and after == before == bytes(rows[3])
     finally:
         c.close()
+
+
+# ---- 8b. the halves are the segments call's and the rows call's, bit for bit --------------------------------------------------------
+def test_the_halves_are_the_other_two_calls_byte_for_byte(eng, orc, case65):
+    """csrc/straus.h holds each loop once, so a mixed row without static scalars runs the operations of the segments call on the same offsets and
+    a mixed row without dynamic terms those of the rows call: the RAW160 sums (the limbs as the kernels leave them, before any compression) are
+    to be equal as bytes, not only as points.  LANE with rows of 0, 1, 2, MSM_SEGMENT_DIRECT_MAX - 1 and MSM_SEGMENT_DIRECT_MAX terms against
+    k_mid_seg_straus, WAVE with longer rows against k_mid_seg_wave; then one point that does not decode, so that the ok bytes and the NONE
+    status are compared too.  Every comparison runs and prints its figure before the one assertion on the sums.  (An empty row
+    runs the doubling chain on the identity in the segments call and skips it in the mixed rows call: the limbs stored are 0, 1, 1, 0 in both.)"""
+    from curve25519_dalek_amd.engine import MSM_SEGMENT_DIRECT_MAX as D, MSM_SEGMENT_WAVE_MAX as X
+    c = case65
+    enc = eng.compress_batch(c.dp_raw, ED)                   # (so that a point can fail to decode: RAW160 inputs are trusted)
+    differ = []
+    for route, lens in ((LANE, (0, 1, 2, D - 1, D)), (WAVE, (D + 1, D + 2, 2 * D + 1))):
+        assert all(n <= D for n in lens) if route == LANE else all(D < n and 8 * n < X for n in lens)
+        off = _off(lens)
+        nd, m = int(off[-1]), len(lens)
+        plan = eng.msm_vartime_segments_plan(off)
+        assert plan[:3] == ((m, 0, 0) if route == LANE else (0, m, 0)), plan
+        ds, dp = c.ds[:nd], enc[:nd].copy()
+        none = np.zeros((m, 0, 32), np.uint8)                # w = 0: the handle has 65 points, only w > n is refused
+        for bad_row in (None, m - 1):
+            if bad_row is not None:
+                dp[int(off[bad_row + 1]) - 1] = np.frombuffer(corpus.bad_point_encoding(orc), np.uint8)
+            st, out, ok = eng.precomp_msm_vartime_mixed_rows(c.h, none, ds, dp, off, ED, route, RAW)
+            st_s, out_s, ok_s = eng.msm_vartime_segments(ds, dp, off, ED, RAW)
+            assert st == st_s == (0 if bad_row is None else 1), (route, bad_row, st, st_s)
+            assert [int(x) for x in ok] == [int(x) for x in ok_s] == [0 if r == bad_row else 1 for r in range(m)], (route, bad_row)
+            for r in range(m):
+                if bytes(out[r]) != bytes(out_s[r]):
+                    differ.append(("segments", route, bad_row, lens[r]))
+                    print("route %d, undecodable point in row %s, row of %d terms: mixed rows %s, segments %s"
+                          % (route, bad_row, lens[r], bytes(out[r]).hex(), bytes(out_s[r]).hex()))
+    m, E0 = 5, np.zeros(6, np.uint64)
+    for w in (1, 3):
+        ss = np.ascontiguousarray(c.s[:m, :w])
+        for route in (LANE, WAVE):
+            st, out, ok = eng.precomp_msm_vartime_mixed_rows(c.h, ss, E32, E160, E0, RAW, route, RAW)
+            rows = eng.precomp_msm_vartime_rows(c.h, ss, route, RAW)
+            assert st == 0 and ok.all() and out.shape == rows.shape == (m, 160)
+            differ += [("rows", route, w, r) for r in range(m) if bytes(out[r]) != bytes(rows[r])]
+    print("comparisons whose RAW160 bytes differ: %s" % differ)
+    assert differ == []
 
 
 # ---- 9. the other front ends ------------------------------------------------------------------------------------------------------
