@@ -115,7 +115,7 @@ def test_double_and_compress_batch(eng, orc):
     raw[1] = np.frombuffer(t4, np.uint8)
     raw[2] = np.frombuffer(orc.ed_add(raw[5].tobytes(), t4), np.uint8)
     got = eng.double_and_compress_batch(raw)
-    for i in list(range(40)) + list(range(40, n, 53)):
+    for i in range(n):                                 # every row (the chain shapes and zero placements: tests/test_gpu_finish_shapes.py)
         want = orc.ris_compress(orc.ed_double(raw[i].tobytes()))
         assert got[i].tobytes() == want, i
     assert not got[0].any() and not got[1].any()       # 2*identity and 2*(4-torsion) encode as the identity
@@ -134,8 +134,7 @@ def test_scalar_invert_batch(eng):
     for i, v in enumerate(vals):
         w = pow(v, -1, L)
         want_prod = want_prod * w % L
-        if i < 64 or i % 37 == 0:
-            assert int.from_bytes(inv[i].tobytes(), "little") == w, i
+        assert int.from_bytes(inv[i].tobytes(), "little") == w, i
     assert int.from_bytes(prod, "little") == want_prod
     e, p = eng.scalar_invert_batch(np.zeros((0, 32), np.uint8))
     assert e.shape == (0, 32) and int.from_bytes(p, "little") == 1

@@ -272,10 +272,10 @@ ks = [rng.randbytes(32) for _ in range(600)]; us = [rng.randbytes(32) for _ in r
 ks[0] = b"\xff" * 32; us[1] = b"\xff" * 32; us[2] = bytes(32)
 arr = lambda xs: np.frombuffer(b"".join(xs), np.uint8).reshape(-1, 32).copy()
 got = e.montgomery_mul_batch(arr(ks), arr(us))
-assert all(bytes(got[i]) == M.mul(us[i], ks[i]) for i in range(0, 600, 13))
+assert all(bytes(got[i]) == M.mul(us[i], ks[i]) for i in range(600))
 bits = np.frombuffer(rng.randbytes(600 * 64), np.uint8).reshape(600, 64).copy()
 got = e.montgomery_mul_bits_be_batch(bits, 512, arr(us))
-assert all(bytes(got[i]) == M.mul_bits_be(us[i], list(np.unpackbits(bits[i]))) for i in range(0, 600, 61))
+assert all(bytes(got[i]) == M.mul_bits_be(us[i], list(np.unpackbits(bits[i]))) for i in range(600))
 e.montgomery_mul_base_batch(arr(ks))
 sg = np.frombuffer(rng.randbytes(600), np.uint8).copy()
 for fmt in (0, 2):

@@ -218,10 +218,12 @@ def test_msm_config4_2p24_terms(eng, orc):
 
 
 def test_msm_affine_and_projective_lanes_mixed(eng, orc):
-    """k_prep_raw takes a direct path for a lane whose sixteen points all have Z = 1 (points straight from a
-    decompression): lanes of both kinds in one launch, and lanes with both kinds of points, give the MSM of the
-    all-projective representation of the same points."""
-    n = 1 << 14                                             # 1024 lanes x 16 points, lane t owns t, t + 1024, ...
+    """2^14 raw points take the mid path (csrc/mid.hip, 6144 .. 2^18 raw terms): k_mid_front reads them as they are, projective
+    or with Z = 1 (points straight from a decompression), and nothing is inverted.  Both kinds in one call -- in blocks of 512, in
+    halves, all affine, one of every three affine -- give the MSM of the all-projective representation of the same points.
+    (The normaliser k_prep_raw2, whose lanes skip their inversion when all their points have Z = 1, no longer sees a call of this
+    size: tests/test_gpu_normaliser_shapes.py drives it.)"""
+    n = 1 << 14
     x = util.rand_scalars(91, n)
     proj = eng.mul_base_batch(util.rand_scalars(92, n), out_fmt=2)
     st, aff, ok = eng.decompress_batch(eng.compress_batch(proj))
@@ -232,8 +234,8 @@ def test_msm_affine_and_projective_lanes_mixed(eng, orc):
     st, want = eng.msm_vartime(x, proj, in_fmt=2)
     assert st == 0
     idx = np.arange(n)
-    for mask in ((idx % 1024) < 512,                        # whole lanes affine, whole lanes projective
-                 idx < n // 2,                              # every lane: 8 affine then 8 projective points
+    for mask in ((idx % 1024) < 512,                        # blocks of 512 affine, 512 projective
+                 idx < n // 2,                              # the first half affine, the second projective
                  np.ones(n, bool),                          # everything affine
                  (idx % 3) == 0):
         pts = np.where(mask[:, None], aff, proj)

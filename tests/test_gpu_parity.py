@@ -129,8 +129,7 @@ def test_x25519_public_keys_through_the_fixed_base_path(eng, orc, golden, torch)
     d9 = torch.zeros((n, 32), dtype=torch.uint8, device="cuda"); d9[:, 0] = 9
     pub = eng.x25519_base_batch_t(dk)
     assert torch.equal(pub, eng.x25519_batch_t(dk, d9))
-    idx = torch.arange(0, n, 97, device="cuda")
-    assert np.array_equal(pub[idx].cpu().numpy(), orc.x25519_batch(dk[idx].cpu().numpy(), d9[idx].cpu().numpy(), threads=8))
+    assert np.array_equal(pub.cpu().numpy(), orc.x25519_batch(dk.cpu().numpy(), d9.cpu().numpy(), threads=8))      # every row
     assert eng.x25519_base_batch(np.zeros((0, 32), np.uint8)).shape == (0, 32)
 
 
@@ -197,7 +196,7 @@ def test_to_montgomery_batch_vs_oracle(eng, orc):
     raw = eng.mul_base_batch(s, out_fmt=2)
     got = eng.to_montgomery_batch(raw)
     assert not got[0].any() and not got[17].any()
-    for i in list(range(0, 5000, 97)) + [1, 16, 18, 4999]:
+    for i in range(5000):                      # every row (the chain shapes and zero placements: tests/test_gpu_finish_shapes.py)
         assert got[i].tobytes() == orc.ed_to_montgomery(raw[i].tobytes()), i
     # and it agrees with the ladder from the basepoint u = 9 (montgomery.rs:628-641)
     nine = np.zeros((64, 32), np.uint8); nine[:, 0] = 9

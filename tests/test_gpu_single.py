@@ -77,7 +77,7 @@ def test_double_base_batch_vs_oracle(eng, orc, golden):
     A = eng.mul_base_batch(util.rand_scalars(73, n), out_fmt=2)                 # raw points with Z != 1
     out, ok = eng.double_base_batch(a, A, b, in_fmt=2, out_fmt=0)
     assert ok.all()
-    for i in list(range(0, 40)) + list(range(40, n, 9)):
+    for i in range(n):
         want = orc.ed_compress(orc.ed_double_scalar_mul_basepoint(a[i].tobytes(), A[i].tobytes(), b[i].tobytes()))
         assert out[i].tobytes() == want, i
     raw, _ = eng.double_base_batch(a[:64], A[:64], b[:64], in_fmt=2, out_fmt=2)
