@@ -1,6 +1,6 @@
 """ed25519_verify_batch_segments: many independent batches in one call.  status[s] must be what verify_batch gives for segment s alone -- expected values
 come from tests/corpus.py (the oracle on the identical segment; for the device z-mode the batch equation evaluated with the z_i of the segment alone,
-eng.debug_batch_zs on that segment) or from the defect that was planted, never from the call under test."""
+the specification in tests/pyref.py device_zs on that segment) or from the defect that was planted, never from the call under test."""
 import itertools
 
 import numpy as np
@@ -201,8 +201,11 @@ def test_corpus_segments(eng, orc, pool, pool_points, z_mode, keys, ptr):
             _CORPUS_ORACLE[keys] = corpus.expect_transcript(orc, segs)
         want = _CORPUS_ORACLE[keys]
     else:
-        # the z_i of the segment ALONE: a wrong tag, length or level in the segment's tree flips a T verdict
-        want = [corpus.predict(orc, g[2], g[3], g[4], eng.debug_batch_zs(g[2], g[3], g[4], 1), [g[5]], True) for g in segs]
+        # the z_i of the segment ALONE, from the specification (tests/pyref.py device_zs), not from the engine: a wrong tag, length or level in the
+        # segment's tree flips a T verdict
+        import pyref
+        want = [corpus.predict(orc, g[2], g[3], g[4], pyref.device_zs([corpus.hram(m, s, k) for m, s, k in zip(g[2], g[3], g[4])], [s[32:] for s in g[3]]),
+                               [g[5]], True) for g in segs]
     want = np.array(want, np.uint8)
     t = np.array([g[0] == "T" for g in segs])
     assert OK in want[t] and VERIFY in want[t], "the T vectors must show both verdicts"
