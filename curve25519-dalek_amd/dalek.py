@@ -18,6 +18,8 @@ error behaviour), batched, on top of Engine.  Reference entry points mirrored:
                                               traits.rs:304-419   (vartime_multiscalar_mul_many)
   Vartime{Edwards,Ristretto}Precomputation::vartime_mixed_multiscalar_mul, many rows of static scalars plus each row's own dynamic terms in one call
                                               traits.rs:304-419, precomputed_straus.rs:29-127   (vartime_mixed_multiscalar_mul_many)
+  the random-linear-combination fold of many such equations into ONE multiscalar mul, as ed25519-dalek/src/batch.rs:207-233 folds signatures
+                                              (vartime_mixed_multiscalar_mul_folded; without a precomputation vartime_multiscalar_mul_folded)
   RistrettoPoint::double_and_compress_batch   curve25519-dalek/src/ristretto.rs:564
   Scalar::invert_batch                        curve25519-dalek/src/scalar.rs:802
   EdwardsBasepointTable::create / mul_base    curve25519-dalek/src/edwards.rs:1131-1141 / :1192-1209   (any basepoint)
@@ -114,6 +116,15 @@ class EdwardsPoint:
         engine.MSM_SEGMENT_WAVE_MAX terms (Bulletproofs-size equations included) all run inside the one call, one GPU lane or one wave each;
         a longer one costs a single-MSM call of its own (Engine.msm_vartime_segments_plan tells which)."""
         return _msm_many(scalar_lists, point_lists, _e.FMT_EDWARDS_Y, engine)
+
+    @staticmethod
+    def vartime_multiscalar_mul_folded(scalar_lists, point_lists, weights, engine=None):
+        """sum_k weights[k] * vartime_multiscalar_mul(scalar_lists[k], point_lists[k]) as ONE multiscalar mul (every scalar times its sum's
+        weight mod l, the fold of ed25519-dalek/src/batch.rs:207-233): CompressedEdwardsY bytes, or None if a point does not decompress.
+        weights: one 16-byte (128-bit, as batch.rs draws them) or 32-byte little-endian integer per sum.  The equations sum_i s_i P_i = 0 all
+        hold iff (up to the weights' randomness) the result is the identity encoding.  Exact for torsion-free points; a point with torsion
+        changes the result by a small-order point, as in verify_batch."""
+        return _msm_folded(scalar_lists, point_lists, weights, _e.FMT_EDWARDS_Y, engine)
 
     @staticmethod
     def vartime_double_scalar_mul_basepoint(a, A, b, engine=None):
@@ -264,6 +275,11 @@ class RistrettoPoint:
         return _msm_many(scalar_lists, point_lists, _e.FMT_RISTRETTO, engine)
 
     @staticmethod
+    def vartime_multiscalar_mul_folded(scalar_lists, point_lists, weights, engine=None):
+        """EdwardsPoint.vartime_multiscalar_mul_folded over CompressedRistretto points (exact: the Ristretto group has prime order l)"""
+        return _msm_folded(scalar_lists, point_lists, weights, _e.FMT_RISTRETTO, engine)
+
+    @staticmethod
     def from_uniform_bytes(inputs, engine=None):
         """[RistrettoPoint::from_uniform_bytes(b_i).compress()] for 64-byte inputs (ristretto.rs:774)"""
         _check_width(inputs, 64, "from_uniform_bytes")
@@ -379,6 +395,29 @@ def _msm_many(scalar_lists, point_lists, fmt, engine):
     eng = engine or default_engine()
     _, out, ok = eng.msm_vartime_segments(_cat([x for s in scalar_lists for x in s], 32), _cat([x for p in point_lists for x in p], 32), off, fmt, fmt)
     return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+
+def _weights(weights, m):
+    """m weights of one width, 16 or 32 bytes -> (m, width) uint8"""
+    weights = [bytes(x) for x in weights]
+    if len(weights) != m:
+        raise AssertionError("folded multiscalar mul: one weight per row")
+    width = len(weights[0]) if weights else 16
+    if width not in (16, 32) or any(len(x) != width for x in weights):
+        raise AssertionError("folded multiscalar mul: weights must all have 16 or all have 32 bytes")
+    return _cat(weights, width)
+
+
+def _msm_folded(scalar_lists, point_lists, weights, fmt, engine):
+    if len(scalar_lists) != len(point_lists) or any(len(s) != len(p) for s, p in zip(scalar_lists, point_lists)):
+        raise AssertionError("vartime_multiscalar_mul: scalars and points must have equal length")
+    m = len(scalar_lists)
+    off = np.zeros(m + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(s) for s in scalar_lists], dtype=np.uint64)
+    eng = engine or default_engine()
+    st, out = eng.precomp_msm_vartime_mixed_rows_fold(None, np.zeros((m, 0, 32), np.uint8), _cat([x for s in scalar_lists for x in s], 32),
+                                                      _cat([x for p in point_lists for x in p], 32), off, _weights(weights, m), fmt, fmt)
+    return None if st == _e.NONE else out
 
 
 def _group_add(ps, qs, op, fmt, what, engine):
@@ -725,6 +764,25 @@ class VartimeEdwardsPrecomputation:
         st, out, ok = self.eng.precomp_msm_vartime_mixed_rows(self.h, ss, _cat([x for _, b, _ in rows for x in b], 32), _cat([x for _, _, c in rows for x in c], 32),
                                                               off, self._fmt, _e.PRECOMP_ROWS_AUTO, self._fmt)
         return [out[i].tobytes() if ok[i] else None for i in range(out.shape[0])]
+
+    def vartime_mixed_multiscalar_mul_folded(self, rows, weights):
+        """sum_r weights[r] * vartime_mixed_multiscalar_mul(*rows[r]) as ONE multiscalar mul: rows as for vartime_mixed_multiscalar_mul_many (any
+        number of dynamic terms per row), weights one 16-byte (128-bit, as ed25519-dalek/src/batch.rs:207-233 draws them) or 32-byte
+        little-endian integer per row -> the 32-byte encoding of the point, or None if a dynamic point does not decode.  The m equations
+        "row r sums to the identity" all hold iff (up to the weights' randomness) the result is the identity encoding; to find a bad row,
+        run vartime_mixed_multiscalar_mul_many.  Scalars are multiplied by their row's weight mod l on the GPU: exact in the Ristretto group
+        and for torsion-free Edwards points (a point with torsion changes the result by a small-order point, as in verify_batch).  No comb
+        table is built."""
+        rows = [(list(a), list(b), list(c)) for a, b, c in rows]
+        if any(len(b) != len(c) for _, b, c in rows):
+            raise AssertionError("dynamic scalars and points must have equal length")   # precomputed_straus.rs:87
+        w = max([len(a) for a, _, _ in rows], default=0)
+        zero = bytes(32)
+        ss = _cat([x for a, _, _ in rows for x in a + [zero] * (w - len(a))], 32).reshape(len(rows), w, 32)
+        off = np.cumsum([0] + [len(b) for _, b, _ in rows]).astype(np.uint64)
+        st, out = self.eng.precomp_msm_vartime_mixed_rows_fold(self.h, ss, _cat([x for _, b, _ in rows for x in b], 32), _cat([x for _, _, c in rows for x in c], 32),
+                                                               off, _weights(weights, len(rows)), self._fmt, self._fmt)
+        return None if st == _e.NONE else out
 
     def close(self):
         if self.h:

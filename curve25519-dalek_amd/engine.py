@@ -134,6 +134,9 @@ _SIGS = {
     "c25519_precomp_msm_vartime_mixed_rows_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, C.c_int, _vp, _i32, C.c_int, _vp, _vp]),
     "c25519_precomp_msm_vartime_mixed_rows": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, C.c_int, _vp, _i32, C.c_int, _vp, _vp]),
     "c25519_precomp_msm_vartime_mixed_rows_plan": (_i32, [_u64, _u64, _vp, _vp]),
+    "c25519_precomp_msm_vartime_mixed_rows_fold_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, C.c_int, _vp, _vp, _i32, C.c_int, _vp]),
+    "c25519_precomp_msm_vartime_mixed_rows_fold": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, C.c_int, _vp, _vp, _i32, C.c_int, _vp]),
+    "c25519_precomp_msm_vartime_mixed_rows_fold_plan": (_i32, [_u64, _u64, _vp, _i32, _vp]),
     "c25519_msm_consttime": (_i32, [_vp, _vp, _vp, _u64, C.c_int, C.c_int, _vp]),
     "c25519_double_and_compress_batch_dev": (_i32, [_vp, _vp, _u64, _vp]),
     "c25519_double_and_compress_batch": (_i32, [_vp, _vp, _u64, _vp]),
@@ -762,6 +765,28 @@ class Engine:
                                                                           in_fmt, off.ctypes.data, route, out_fmt, out.data_ptr(), ok.data_ptr()), (OK, NONE))
         return st, out, ok
 
+    def precomp_msm_vartime_mixed_rows_fold_t(self, h, static_scalars, dyn_scalars, dyn_points, dyn_off, weights, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):
+        """precomp_msm_vartime_mixed_rows_fold on device inputs: static_scalars (m, w, 32), dyn_scalars (n_dyn, 32), dyn_points (n_dyn, 32|160),
+        weights (m, 16) or (m, 32) uint8 CUDA tensors; dyn_off m + 1 offsets on the HOST (a sequence or a CPU tensor); h may be None iff w == 0
+        -> (status OK | NONE, 32|160 bytes on the host), on torch's current stream (the call synchronises it)"""
+        assert static_scalars.dim() == 3 and static_scalars.shape[2] == 32, "static_scalars must have shape (m, w, 32)"
+        m, w = int(static_scalars.shape[0]), int(static_scalars.shape[1])
+        if static_scalars.numel():
+            self._t(static_scalars, 32)
+        n = self._t(dyn_scalars, 32)
+        assert self._t(dyn_points, _PT.get(in_fmt, 32)) == n
+        assert weights.dim() == 2 and int(weights.shape[0]) == m, "weights must have shape (m, 16) or (m, 32)"
+        wb = int(weights.shape[1])
+        if weights.numel():
+            self._t(weights, wb)
+        off = _seg_off_host(dyn_off)
+        assert off.shape[0] == m + 1, "dyn_off must hold m + 1 offsets"
+        out = C.create_string_buffer(_PT.get(out_fmt, 32))
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_precomp_msm_vartime_mixed_rows_fold_dev(self.ctx, h, static_scalars.data_ptr(), m, w, dyn_scalars.data_ptr(), dyn_points.data_ptr(), n,
+                                                                               in_fmt, off.ctypes.data, weights.data_ptr(), wb, out_fmt, out), (OK, NONE))
+        return st, out.raw
+
     def verify_batch_segments_t(self, msgs, msg_off, sigs, pks, seg_off, z_mode=Z_TRANSCRIPT, pk_points=None):
         """many independent verify_batch calls in one: status[s] is what verify_batch_t returns for signatures [seg_off[s], seg_off[s+1]) alone.
         msgs, msg_off, sigs, pks, pk_points as for verify_batch_t (CUDA tensors); seg_off m + 1 offsets on the HOST -> (m,) uint8 CUDA tensor"""
@@ -1201,6 +1226,45 @@ class Engine:
         if st < 0:
             raise EngineError("HIP error %d: precomp_msm_vartime_mixed_rows_plan: m must be below 2^32 - 1, m * w must not overflow, dyn_off must be m + 1 "
                               "non-decreasing values from 0, below 2^40, and no row may have more than MSM_SEGMENT_WAVE_MAX dynamic terms" % -st)
+        return tuple(int(x) for x in plan)
+
+    def precomp_msm_vartime_mixed_rows_fold(self, h, static_scalars, dyn_scalars, dyn_points, dyn_off, weights, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):
+        """the rows of precomp_msm_vartime_mixed_rows folded into ONE multiscalar mul by a random linear combination (the fold of
+        ed25519-dalek/src/batch.rs:207-233 for the equations of vartime_mixed_multiscalar_mul): with a weight c_r per row, on integers mod l,
+        t_j = sum_r c_r * static_scalars[r][j], d'_i = c_row(i) * dyn_scalars[i], out = sum_j t_j * S_j + sum_i d'_i * dyn_points[i].
+        static_scalars (m, w, 32), dyn_scalars (n_dyn, 32), dyn_points (n_dyn, 32|160) uint8, dyn_off m + 1 offsets, weights (m, 16) or (m, 32)
+        uint8 -> (status OK | NONE, 32|160 bytes).  Scalars and weights are any little-endian integers (reduced by the product: no bit-255
+        refusal); a row may have any number of dynamic terms; h may be None iff w == 0.  The result in format 0 or 1 is byte for byte
+        precomp_msm_vartime(h, t, d', dyn_points); exact in the Ristretto group and for torsion-free Edwards points (a point with torsion
+        changes it by a small-order point, as in verify_batch).  No comb table is built (precomp_rows_table_bytes is unchanged)."""
+        ss = np.ascontiguousarray(static_scalars, dtype=np.uint8)
+        assert ss.ndim == 3 and ss.shape[2] == 32, "static_scalars must have shape (m, w, 32)"
+        m, w = ss.shape[0], ss.shape[1]
+        ds = _np8(dyn_scalars, 32) if len(dyn_scalars) else np.zeros((0, 32), np.uint8)
+        dp = _np8(dyn_points, _PT.get(in_fmt, 32)) if len(dyn_points) else np.zeros((0, _PT.get(in_fmt, 32)), np.uint8)
+        assert ds.shape[0] == dp.shape[0]
+        off = np.ascontiguousarray(np.asarray(dyn_off, dtype=np.uint64).reshape(-1))
+        assert off.shape[0] == m + 1, "dyn_off must hold m + 1 offsets"
+        wt = np.ascontiguousarray(weights, dtype=np.uint8)
+        assert wt.ndim == 2 and wt.shape[0] == m, "weights must have shape (m, 16) or (m, 32)"
+        out = C.create_string_buffer(_PT.get(out_fmt, 32))
+        self._bind_stream()
+        st = self._chk(self.lib.c25519_precomp_msm_vartime_mixed_rows_fold(self.ctx, h, ss.ctypes.data, m, w, ds.ctypes.data, dp.ctypes.data, ds.shape[0], in_fmt,
+                                                                           off.ctypes.data, wt.ctypes.data, wt.shape[1], out_fmt, out), (OK, NONE))
+        return st, out.raw
+
+    @staticmethod
+    def precomp_msm_vartime_mixed_rows_fold_plan(m, w, dyn_off, weight_bytes=16):
+        """the MSM precomp_msm_vartime_mixed_rows_fold leaves behind and how its column fold is cut -> (static terms of the final MSM, its dynamic
+        terms, row slices of the column fold, rows per slice).  Host arithmetic: needs no GPU and no context (a static method); a shape the
+        call would reject raises."""
+        off = np.ascontiguousarray(np.asarray(dyn_off, dtype=np.uint64).reshape(-1))
+        assert m == 0 or off.shape[0] == m + 1, "dyn_off must hold m + 1 offsets"
+        plan = np.zeros(4, np.uint64)
+        st = load_library().c25519_precomp_msm_vartime_mixed_rows_fold_plan(m, w, off.ctypes.data if off.size else None, weight_bytes, plan.ctypes.data)
+        if st < 0:
+            raise EngineError("HIP error %d: precomp_msm_vartime_mixed_rows_fold_plan: weight_bytes must be 16 or 32, m below 2^32 - 1, m * w must not overflow, "
+                              "dyn_off must be m + 1 non-decreasing values from 0, below 2^40" % -st)
         return tuple(int(x) for x in plan)
 
     def msm_consttime(self, scalars, points, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):

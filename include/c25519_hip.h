@@ -654,6 +654,54 @@ int32_t c25519_precomp_msm_vartime_mixed_rows(c25519_ctx *ctx, c25519_precomp *p
  * below 2^32 - 1.  Host arithmetic: no context, no GPU. */
 int32_t c25519_precomp_msm_vartime_mixed_rows_plan(uint64_t m, uint64_t w, const uint64_t *dyn_off, uint64_t plan[4]);
 
+/* The rows of the mixed rows call FOLDED into ONE multiscalar mul by a random linear combination: with a weight c_r per row, all on integers mod l,
+ *   t_j = sum_r c_r * static_scalars[r][j]  (j < w),   d'_i = c_row(i) * dyn_scalars[i],   out = sum_j t_j * S_j + sum_i d'_i * dyn_points[i]
+ * -- what a verifier runs on its common path: m verification equations hold iff (up to the weights' randomness) this ONE sum is the identity.
+ * It is the fold of ed25519-dalek/src/batch.rs:207-233 (128-bit z_i, the scalars z_i * s_i and z_i * k_i mod l, one
+ * VartimeMultiscalarMul::vartime_multiscalar_mul), offered for the equations of VartimePrecomputedMultiscalarMul::vartime_mixed_multiscalar_mul
+ * (traits.rs:304-419, precomputed_straus.rs:29-127) instead of signatures only.  The per-row calls above stay what locates a bad row.
+ *   - static_scalars m x w x 32, row-major; dyn_scalars n_dyn x 32; dyn_points n_dyn x 32 | 160 in in_fmt, the rows' terms one after the other;
+ *     weights m x weight_bytes: HOST pointers in the un-suffixed form, DEVICE pointers (16-byte aligned) in the _dev form.  dyn_off is a HOST array
+ *     of m + 1 offsets and out a HOST pointer (32 | 160 bytes) in BOTH forms, and both synchronise, as c25519_msm_vartime_dev does.
+ *   - static scalars, dynamic scalars and 32-byte weights are ANY 32-byte little-endian integers: the products reduce them mod l, so -- unlike the
+ *     sibling calls -- nothing is refused for bit 255; the scalars that reach the MSM are canonical by construction.  16-byte weights are 128-bit
+ *     integers, the width of z_i in batch.rs.
+ *   - p: the first w static points of the handle are used, w <= c25519_precomp_len(p); a handle of ANY size is accepted, because no comb table is
+ *     involved (c25519_precomp_rows_table_bytes does not change).  p == NULL is allowed iff w == 0: the fold of c25519_msm_vartime_segments.
+ *   - a row may have any number of dynamic terms (the rows end up in one MSM: C25519_MSM_SEGMENT_WAVE_MAX does not apply).
+ *   - each of these returns -(hipErrorInvalidValue) before any launch: weight_bytes other than 16 or 32; out_fmt outside 0 .. 2; w above
+ *     c25519_precomp_len (precomputed_straus.rs:86) or w != 0 without a handle; in_fmt and out_fmt of different groups (the pairing rule of
+ *     c25519_msm_vartime_segments); dyn_off[0] != 0, a decreasing pair, dyn_off[m] != n_dyn, n_dyn not below 2^40; m not below 2^32 - 1; m * w
+ *     overflowing.  m == 0 writes the identity.
+ *   - the result in format 0 or 1 is byte for byte what c25519_precomp_msm_vartime returns for (t, d', dyn_points); a RAW160 output is the same
+ *     point (equal under ct_eq), not the same limbs.  Returns C25519_NONE iff a dynamic point does not decode; out is then unspecified.
+ * CAVEAT: reducing mod l changes the result by a small-order point when an Edwards input is not torsion-free -- the property of
+ * ed25519_verify_batch (batch.rs:207-233 multiplies by z_i mod l as well).  The result is exact in the Ristretto group and for torsion-free
+ * points.  The weights are the caller's randomness; the call is variable time, its scalars and weights are public by contract.
+ * How: two small kernels of scalar arithmetic (28-bit limbs, l = 2^252 + c folded directly) -- the weighted column sums, lanes on consecutive
+ * columns of a row and rows cut into slices so that about 512 blocks run whatever the shape (c25519_precomp_msm_vartime_mixed_rows_fold_plan),
+ * and one lane per dynamic term -- then the MSM the library has: the static half over the handle's bucket table, the dynamic half through the
+ * routed device-resident MSM (c25519_msm_partial_dev: small, mid or bucket path by n_dyn), added on the host.  c25519_phase_ms(ctx, 0, 0 | 1)
+ * after the call: the column fold | the dynamic scaling.
+ * Measured by tools/precomp_fold_numbers.py (profiles/precomp_fold_numbers.txt), device-resident, 16-byte weights, ms:
+ * the call against c25519_precomp_msm_vartime_mixed_rows_dev on the same input and against the final MSM alone on pre-folded scalars:
+ * 4096 rows of 130 + 17: 0.63 against 3.79 and 0.59 (the fold kernels 0.08); 256 of 2050 + 40: 0.45 against 6.68 and 0.44; 131072 of 2 + 1: 0.61
+ * against 2.30 and 0.51; 2^20 of 1 + 2: 2.66 against 18.95 and 2.06 -- there 0.6 ms above the MSM alone, 0.29 of it the kernels, the rest the
+ * upload of 8 MB of dyn_off; 64 of 2 + 1: 0.26 against 0.83 and 0.25.  The fold is the faster of the two calls from m = 1. */
+int32_t c25519_precomp_msm_vartime_mixed_rows_fold_dev(c25519_ctx *ctx, const c25519_precomp *p, const uint8_t *d_static_scalars /* m x w x 32, row-major */, uint64_t m,
+                                                       uint64_t w, const uint8_t *d_dyn_scalars /* n_dyn x 32 */, const uint8_t *d_dyn_points /* n_dyn x (32 | 160) */,
+                                                       uint64_t n_dyn, int in_fmt, const uint64_t *dyn_off /* m + 1 HOST offsets */,
+                                                       const uint8_t *d_weights /* m x weight_bytes */, int32_t weight_bytes /* 16 | 32 */, int out_fmt,
+                                                       uint8_t *out /* HOST, 32 | 160 */);
+int32_t c25519_precomp_msm_vartime_mixed_rows_fold(c25519_ctx *ctx, const c25519_precomp *p, const uint8_t *static_scalars, uint64_t m, uint64_t w,
+                                                   const uint8_t *dyn_scalars, const uint8_t *dyn_points, uint64_t n_dyn, int in_fmt, const uint64_t *dyn_off,
+                                                   const uint8_t *weights, int32_t weight_bytes, int out_fmt, uint8_t *out);
+/* the MSM the fold leaves behind and how the column fold is cut: plan[0] static terms of the final MSM (w), plan[1] its dynamic terms (dyn_off[m]),
+ * plan[2] the row slices of the column fold, plan[3] the rows per slice (plan[2] * plan[3] >= m > (plan[2] - 1) * plan[3]).  Same refusals and the
+ * same error as the call, as far as they depend on (m, w, dyn_off, weight_bytes); dyn_off[m] is read only once m is known to be below 2^32 - 1.
+ * Host arithmetic: no context, no GPU. */
+int32_t c25519_precomp_msm_vartime_mixed_rows_fold_plan(uint64_t m, uint64_t w, const uint64_t *dyn_off, int32_t weight_bytes, uint64_t plan[4]);
+
 /* ---- regular-schedule multiscalar multiplication: MultiscalarMul::multiscalar_mul ------------------------
  * replaces backend::straus_multiscalar_mul (backend.rs:196 -> scalar_mul/straus.rs:103-144;
  * edwards.rs:966-1000).  One radix-16 fixed-window ladder per term (the schedule of variable_base.rs: identical
