@@ -14,7 +14,8 @@
 //   k_mid_seg_wave     one WAVE per segment of at most C25519_MSM_SEGMENT_WAVE_MAX terms (the loop of straus_dyn_wave): lane l takes terms l, l + 64,
 //                      l + 128, ... and runs the same window loop over them; the 64 partial sums are folded across the wave with six shuffle
 //                      rounds.  (The constant is measured; the kernel itself is correct for any length.)
-// Compressed outputs go through c25519_compress_batch_dev (no second inversion here).  Segments longer than the wave maximum run through
+// Compressed outputs go through c25519_compress_batch_dev (no second inversion here).  Segments longer than the wave maximum and at most
+// C25519_MSM_SEGMENT_BUCKET_MAX terms take the bucket route (mid_segb.hip: three launches per pass of such segments); still longer ones run through
 // c25519_msm_partial_dev, one call each, and their sums are placed beside the others before that finishing step.
 // The scalars are public by contract (a *_vartime entry point): branches and table addresses depend on their digits.  Every loop bound comes
 // from the offsets the host validated; the kernels wait for nothing and use no atomics (the two verdict words are set by plain stores of 1).
@@ -23,6 +24,7 @@
 #include <string.h>
 #include <vector>
 #include "straus.h"                         // (and through it devio.h, kernels.h, ctx.h, knobs.h, precomp.h, rows_digits.h, capi_util.h)
+#include "mid_segb.h"                       // the bucket route: its kernels are in mid_segb.hip
 #include "ffi.h"
 
 using namespace c25519;
@@ -105,15 +107,24 @@ static int32_t seg_check(c25519_ctx *ctx, uint64_t n, int in_fmt, const uint64_t
 // ---- routing: the one place that decides which kernel a segment gets and where the passes are cut ----
 //   len <= dmax   lane   (k_mid_seg_straus; empty segments too: they give the identity)
 //   len <= wmax   wave   (k_mid_seg_wave)
+//   len <= bmax   bucket (mid_segb.hip)
 //   longer        the single-MSM path, one c25519_msm_partial_dev each
 // A pass is a run of consecutive lane and wave segments of at most ptmax terms in all (ptmax >= wmax: one segment always fits); only the
-// single-MSM segments and the term count cut it.  The wave kernel of a pass runs over wave_ids[w0 .. w1).
+// segments above wmax (of either kind: n_long counts both) and the term count cut it.  The wave kernel of a pass runs over wave_ids[w0 .. w1).
+// The bucket segments have passes of their own: runs of the list `buckets` of at most bptmax terms in all (bptmax >= bmax).
+static int seg_route_of(uint64_t len) {
+    return len <= seg_direct_max() ? C25519_MSM_SEGMENT_ROUTE_LANE : len <= seg_wave_max() ? C25519_MSM_SEGMENT_ROUTE_WAVE
+         : len <= seg_bucket_max() ? C25519_MSM_SEGMENT_ROUTE_BUCKET : C25519_MSM_SEGMENT_ROUTE_SINGLE;
+}
 struct seg_pass { uint64_t s0, s1, w0, w1, lanes; };       // segments [s0, s1), terms [seg_off[s0], seg_off[s1]); `lanes` of them on the lane route
+struct seg_bpass { uint64_t k0, k1, nt; };                  // buckets[k0 .. k1), nt terms in all
 struct seg_route {
     uint64_t n_lane = 0, n_wave = 0, n_long = 0, n_pass = 0, maxt = 0;      // what c25519_msm_vartime_segments_plan reports
     std::vector<seg_pass> passes;                           // the lists: only when asked for (seg_run)
     std::vector<uint32_t> wave_ids;
-    std::vector<uint64_t> longs;
+    std::vector<uint64_t> longs, buckets;
+    std::vector<seg_bpass> bpasses;
+    uint64_t bmaxt = 0, bmaxseg = 0;                        // most terms / segments of one bucket pass
 };
 static void seg_plan(const uint64_t *seg_off, uint64_t m, bool lists, seg_route &R) {
     const uint64_t dmax = seg_direct_max(), wmax = seg_wave_max(), ptmax = seg_pass_terms();
@@ -127,13 +138,36 @@ static void seg_plan(const uint64_t *seg_off, uint64_t m, bool lists, seg_route 
     };
     for (uint64_t s = 0; s < m; s++) {
         const uint64_t len = seg_off[s + 1] - seg_off[s];
-        if (len > wmax) { close(s); s0 = s + 1; R.n_long++; if (lists) R.longs.push_back(s); continue; }
+        if (len > wmax) {
+            close(s); s0 = s + 1; R.n_long++;
+            if (lists) (seg_route_of(len) == C25519_MSM_SEGMENT_ROUTE_BUCKET ? R.buckets : R.longs).push_back(s);
+            continue;
+        }
         if (terms + len > ptmax) { close(s); s0 = s; }
         terms += len;
         if (len > dmax) { R.n_wave++; if (lists) R.wave_ids.push_back((uint32_t)s); }     // s < m < 2^32 - 1: check_offsets has bounded m
         else { R.n_lane++; lanes++; }
     }
     close(m);
+    const uint64_t bptmax = seg_bucket_pass_terms();
+    for (uint64_t k = 0; k < R.buckets.size();) {
+        seg_bpass p = {k, k, 0};
+        for (; p.k1 < R.buckets.size(); p.k1++) {
+            const uint64_t len = seg_off[R.buckets[p.k1] + 1] - seg_off[R.buckets[p.k1]];
+            if (p.k1 > p.k0 && p.nt + len > bptmax) break;
+            p.nt += len;
+        }
+        R.bmaxt = std::max(R.bmaxt, p.nt); R.bmaxseg = std::max(R.bmaxseg, p.k1 - p.k0);
+        R.bpasses.push_back(p);
+        k = p.k1;
+    }
+}
+
+EXPORT int32_t c25519_msm_vartime_segments_routes(const uint64_t *seg_off, uint64_t m, uint8_t *route) {
+    int32_t r;
+    if ((r = check_offsets(nullptr, SEG_OFF_MSGS, offsets_end(seg_off, m), seg_off, m))) return r;
+    for (uint64_t s = 0; s < m; s++) route[s] = (uint8_t)seg_route_of(seg_off[s + 1] - seg_off[s]);
+    return C25519_OK;
 }
 
 EXPORT int32_t c25519_msm_vartime_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[5]) {
@@ -170,18 +204,33 @@ static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
         } else if (r) return r;
     }
     // tmp_f (straus_ws): seg_off | segment ids of the wave route, pass after pass | raw sums | ok | tables | digits | term ok bytes
+    // The bucket passes (segb_ws) use the place of the last three -- the passes of the two kinds run one after the other on the stream -- and
+    // their descriptors lie behind it.
     straus_ws ws(m, R.wave_ids.size(), maxt, out_fmt, d_ok != nullptr);
+    std::vector<uint64_t> bdesc;                            // the descriptors of all bucket passes, pass after pass (mid_segb.h)
+    for (const seg_bpass &p : R.bpasses) {
+        uint64_t at = 0;
+        for (uint64_t k = p.k0; k < p.k1; k++) { bdesc.push_back(at); at += seg_off[R.buckets[k] + 1] - seg_off[R.buckets[k]]; }
+        bdesc.push_back(at);
+        for (uint64_t k = p.k0; k < p.k1; k++) bdesc.push_back(seg_off[R.buckets[k]]);
+        for (uint64_t k = p.k0; k < p.k1; k++) bdesc.push_back(R.buckets[k]);
+    }
+    segb_ws bw(R.bmaxt, R.bmaxseg, bdesc.size());
+    const size_t ws_head = ws.b_off + ws.b_ids + ws.b_sum + ws.b_ok, ws_pass = std::max(ws.b_tab + ws.b_dig + ws.b_tok, bw.pass_bytes());
     int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, ws.bytes()))) return r;
+    if ((r = ctx_reserve(ctx, ctx->tmp_f, ws_head + ws_pass + bw.b_desc + 256))) return r;
     ws.carve((uint8_t *)ctx->tmp_f.p, d_out, d_ok);
+    bw.carve((uint8_t *)ctx->tmp_f.p + ws_head, (uint8_t *)ctx->tmp_f.p + ws_head + ws_pass);
     uint32_t *flags = (uint32_t *)ctx->d_flag;
     auto enqueue = [&]() -> int32_t {
         HIPCHK(hipMemsetAsync(flags, 0, 8, st));
         HIPCHK(hipEventRecord(ctx->ev0, st));
         HIPCHK(hipMemcpyAsync(ws.d_off, seg_off, (m + 1) * 8, hipMemcpyHostToDevice, st));
         if (!R.wave_ids.empty()) HIPCHK(hipMemcpyAsync(ws.d_ids, R.wave_ids.data(), R.wave_ids.size() * 4, hipMemcpyHostToDevice, st));
-        ctx->kname[0] = R.wave_ids.empty() ? "c25519::k_mid_seg_straus (one lane per segment, the doubling chain shared by its terms)"
-                                           : "c25519::k_mid_seg_wave (one wave per segment, lane l takes terms l, l + 64, ...; the partial sums folded by shuffles)";
+        if (!bdesc.empty()) HIPCHK(hipMemcpyAsync(bw.desc, bdesc.data(), bdesc.size() * 8, hipMemcpyHostToDevice, st));
+        ctx->kname[0] = !R.wave_ids.empty() ? "c25519::k_mid_seg_wave (one wave per segment, lane l takes terms l, l + 64, ...; the partial sums folded by shuffles)"
+                      : !R.buckets.empty()  ? SEGB_KERNEL_NAME
+                                            : "c25519::k_mid_seg_straus (one lane per segment, the doubling chain shared by its terms)";
         for (const seg_pass &p : passes) {
             const uint64_t t0 = seg_off[p.s0], nt = seg_off[p.s1] - t0, ns = p.s1 - p.s0;
             int32_t q;
@@ -196,6 +245,15 @@ static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
                 hipLaunchKernelGGL(k_mid_seg_wave, dim3(div_up(nw, 4)), dim3(256), 0, st, (const u64 *)ws.d_off, (const u32 *)(ws.d_ids + p.w0), (u32)nw, t0, nt,
                                    (const uint4 *)ws.tab, (const int8_t *)ws.dig, (const uint8_t *)ws.tok, ws.sums, ws.okbuf, flags);
                 HIPCHK(hipGetLastError());
+            }
+        }
+        {                                                   // the bucket passes, behind the Straus passes: three launches each, disjoint outputs
+            size_t at = 0;
+            for (const seg_bpass &p : R.bpasses) {
+                const uint64_t nb = p.k1 - p.k0;
+                int32_t q;
+                if ((q = segb_enqueue_pass(ctx, in_fmt, d_scalars, d_points, bw, bw.desc + at, (uint32_t)nb, p.nt, ws.sums, ws.okbuf))) return q;
+                at += segb_desc_words(nb);
             }
         }
         for (size_t k = 0; k < longs.size(); k++) {

@@ -113,8 +113,9 @@ class EdwardsPoint:
     def vartime_multiscalar_mul_many(scalar_lists, point_lists, engine=None):
         """[vartime_multiscalar_mul(scalar_lists[k], point_lists[k])] for every k in one call: CompressedEdwardsY bytes, or None where a
         point of that sum does not decompress.  Unequal lengths inside a pair raise, as in the single form.  Sums of up to
-        engine.MSM_SEGMENT_WAVE_MAX terms (Bulletproofs-size equations included) all run inside the one call, one GPU lane or one wave each;
-        a longer one costs a single-MSM call of its own (Engine.msm_vartime_segments_plan tells which)."""
+        engine.MSM_SEGMENT_BUCKET_MAX terms all run inside the one call: one GPU lane or one wave each up to engine.MSM_SEGMENT_WAVE_MAX terms
+        (Bulletproofs-size equations included), the bucket method side by side beyond (aggregated range proofs); a still longer one costs a
+        single-MSM call of its own (Engine.msm_vartime_segments_routes tells which)."""
         return _msm_many(scalar_lists, point_lists, _e.FMT_EDWARDS_Y, engine)
 
     @staticmethod

@@ -174,6 +174,7 @@ _SIGS = {
     "c25519_msm_vartime_segments_dev": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_msm_vartime_segments": (_i32, [_vp, _vp, _vp, _u64, C.c_int, _vp, _u64, C.c_int, _vp, _vp]),
     "c25519_msm_vartime_segments_plan": (_i32, [_vp, _u64, _vp]),
+    "c25519_msm_vartime_segments_routes": (_i32, [_vp, _u64, _vp]),
     "ed25519_verify_batch_segments_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp]),
     "ed25519_verify_batch_segments": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp]),
     "ed25519_verify_batch_segments_plan": (_i32, [_vp, _u64, _vp]),
@@ -218,8 +219,12 @@ def load_library():
 _PT = {FMT_EDWARDS_Y: 32, FMT_RISTRETTO: 32, FMT_RAW160: 160}
 PARTIAL_RECORD_BYTES = 9024      # C25519_PARTIAL_RECORD_BYTES
 MSM_SEGMENT_DIRECT_MAX = 64      # C25519_MSM_SEGMENT_DIRECT_MAX: the longest segment msm_vartime_segments runs one per lane
-MSM_SEGMENT_WAVE_MAX = 2048      # C25519_MSM_SEGMENT_WAVE_MAX: the longest segment it runs one per wave; longer ones take the single-MSM path
+MSM_SEGMENT_WAVE_MAX = 2048      # C25519_MSM_SEGMENT_WAVE_MAX: the longest segment it runs one per wave
 MSM_SEGMENT_PASS_TERMS = 1 << 18     # C25519_MSM_SEGMENT_PASS_TERMS: most terms whose tables are resident at once
+MSM_SEGMENT_BUCKET_MAX = 32768  # C25519_MSM_SEGMENT_BUCKET_MAX: the longest segment on its bucket route; longer ones take the single-MSM path
+MSM_SEGMENT_BUCKET_PASS_TERMS = 1 << 20      # C25519_MSM_SEGMENT_BUCKET_PASS_TERMS: most terms of one pass of the bucket route
+# what msm_vartime_segments_routes reports per segment (C25519_MSM_SEGMENT_ROUTE_*)
+MSM_SEGMENT_ROUTE_LANE, MSM_SEGMENT_ROUTE_WAVE, MSM_SEGMENT_ROUTE_BUCKET, MSM_SEGMENT_ROUTE_SINGLE = 0, 1, 2, 3
 VERIFY_SEGMENT_MAX = 1023        # ED25519_VERIFY_SEGMENT_MAX: the longest segment verify_batch_segments runs through the segmented MSM
 TRANSCRIPT_SEGMENT_DEVICE_MAX = 256      # ED25519_TRANSCRIPT_SEGMENT_DEVICE_MAX: the longest segment whose Merlin transcript verify_batch_segments runs on the device
 PRECOMP_ROWS_MAX_POINTS = 4096   # C25519_PRECOMP_ROWS_MAX_POINTS: the largest handle precomp_msm_vartime_rows serves (64 KB of comb table per point)
@@ -1439,7 +1444,9 @@ class Engine:
     def msm_vartime_segments(self, scalars, points, seg_off, in_fmt=FMT_RAW160, out_fmt=FMT_EDWARDS_Y):
         """many independent vartime MSMs in one call (optional_multiscalar_mul per segment, edwards.rs:1002-1031 / ristretto.rs:984):
         out[s] = sum scalars[i] * points[i] over [seg_off[s], seg_off[s+1]) -> (status OK | NONE, (m, 32|160), ok (m,)); ok[s] = 0 where a
-        point of segment s does not decode.  Routed by length: one lane, one wave or a single-MSM call per segment (msm_vartime_segments_plan)"""
+        point of segment s does not decode.  Routed by length (msm_vartime_segments_routes): one lane per segment up to MSM_SEGMENT_DIRECT_MAX terms,
+        one wave up to MSM_SEGMENT_WAVE_MAX, the bucket method for all such segments side by side up to MSM_SEGMENT_BUCKET_MAX, a single-MSM call
+        per segment beyond"""
         s = _np8(scalars, 32) if len(scalars) else np.zeros((0, 32), np.uint8)
         a = _np8(points, _PT.get(in_fmt, 32)) if len(points) else np.zeros((0, _PT.get(in_fmt, 32)), np.uint8)
         assert s.shape[0] == a.shape[0]
@@ -1454,9 +1461,10 @@ class Engine:
 
     @staticmethod
     def msm_vartime_segments_plan(seg_off):
-        """how msm_vartime_segments routes these m + 1 offsets -> (lane segments, wave segments, single-MSM segments, passes, most terms
-        resident in one pass): at most MSM_SEGMENT_DIRECT_MAX terms run one per lane, at most MSM_SEGMENT_WAVE_MAX one per wave, longer ones
-        through the single-MSM path.  Host arithmetic: needs no GPU and no context (a static method); offsets the call would reject raise."""
+        """how msm_vartime_segments routes these m + 1 offsets -> (lane segments, wave segments, segments longer than the wave maximum, passes
+        of the lane and wave segments, most terms resident in one such pass): at most MSM_SEGMENT_DIRECT_MAX terms run one per lane, at most
+        MSM_SEGMENT_WAVE_MAX one per wave, longer ones on the bucket route or through the single-MSM path (msm_vartime_segments_routes tells
+        which).  Host arithmetic: needs no GPU and no context (a static method); offsets the call would reject raise."""
         off = np.ascontiguousarray(np.asarray(seg_off, dtype=np.uint64).reshape(-1))
         assert off.shape[0] >= 1
         plan = np.zeros(5, np.uint64)
@@ -1464,6 +1472,18 @@ class Engine:
         if st < 0:
             raise EngineError("HIP error %d: msm_vartime_segments_plan: seg_off must be m + 1 non-decreasing values from 0, below 2^40" % -st)
         return tuple(int(x) for x in plan)
+
+    @staticmethod
+    def msm_vartime_segments_routes(seg_off):
+        """the route of every segment of these m + 1 offsets -> (m,) uint8 of MSM_SEGMENT_ROUTE_LANE / _WAVE / _BUCKET / _SINGLE, by its length
+        alone.  Host arithmetic: needs no GPU and no context (a static method); offsets the call would reject raise."""
+        off = np.ascontiguousarray(np.asarray(seg_off, dtype=np.uint64).reshape(-1))
+        assert off.shape[0] >= 1
+        route = np.zeros(off.shape[0] - 1, np.uint8)
+        st = load_library().c25519_msm_vartime_segments_routes(off.ctypes.data, off.shape[0] - 1, route.ctypes.data)
+        if st < 0:
+            raise EngineError("HIP error %d: msm_vartime_segments_routes: seg_off must be m + 1 non-decreasing values from 0, below 2^40" % -st)
+        return route
 
     @staticmethod
     def msm_route(kind, n, in_fmt=FMT_RAW160, host_pointers=False):

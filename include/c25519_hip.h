@@ -263,7 +263,8 @@ int32_t c25519_fold_partials(c25519_ctx *ctx, const uint8_t *partials160, uint64
  *   - both forms synchronise the context's stream once, at the end, to read the two verdict words.
  *   - every out[s] is byte for byte what c25519_msm_vartime returns for that segment alone (canonical encodings); a RAW160 output is the
  *     same point (equal under ct_eq), not the same limbs.
- * Cost: three routes, chosen by the length of each segment alone (c25519_msm_vartime_segments_plan reports the choice).
+ * Cost: four routes, chosen by the length of each segment alone (c25519_msm_vartime_segments_routes reports the choice per segment,
+ * c25519_msm_vartime_segments_plan its counts).
  *   - at most C25519_MSM_SEGMENT_DIRECT_MAX terms: one GPU LANE per segment -- Straus with the doubling chain shared by the terms of the
  *     segment (scalar_mul/straus.rs:159-200), radix 16 -- so a wave of 64 consecutive segments costs what its LONGEST one costs: group
  *     segments of similar length next to each other.
@@ -272,23 +273,43 @@ int32_t c25519_fold_partials(c25519_ctx *ctx, const uint8_t *partials160, uint64
  *     additions per window in every lane, and thousands of such segments run side by side inside the one call.  (A wave would carry
  *     64 x 64 terms at the serial depth of the lane route's maximum; from 64 segments per call on it is not slower than the single-MSM
  *     route up to 2048 terms, which is where the constant stands.  One lone segment is faster through c25519_msm_vartime.)
+ *   - at most C25519_MSM_SEGMENT_BUCKET_MAX terms (aggregated range proofs, large-ring checks): the BUCKET method per segment
+ *     (scalar_mul/pippenger.rs:67-160) at one window width, 8 bits, for all such segments of the call side by side -- one record and 32
+ *     signed digits per term, one workgroup per (segment, window) that sorts the window's digits into 128 bucket lists, adds them up in
+ *     128 equal shares of the entries (so equal scalars cost what uniform ones cost) and reduces the buckets by a suffix scan, then one
+ *     lane per segment for the Horner fold: 32 len bucket additions and 248 doublings per segment, three launches however many segments
+ *     there are, nothing synchronised before the end of the call.  (64 segments of 2049 / 4096 / 32768 terms: 1.25 / 1.61 / 8.0 ms against
+ *     7.5 / 9.5 / 14.3 ms on the single-MSM route; at 65536 terms it loses, which is where the constant stands.  One lone segment is
+ *     faster through c25519_msm_vartime.)
  *   - longer: each segment runs as a c25519_msm_partial_dev of its own before the rest is queued (tens of microseconds of latency apiece,
  *     one after the other).
  * The tables of at most C25519_MSM_SEGMENT_PASS_TERMS terms (1344 bytes per term) are resident at a time; more terms of the first two
- * routes run as several passes, cut at segment boundaries.  tools/seg_msm_numbers.py times the call against one c25519_msm_vartime_dev per
- * segment and against c25519_mul_batch_dev + c25519_point_sum_segments_dev. */
+ * routes run as several passes, cut at segment boundaries.  The bucket segments have passes of their own, of at most
+ * C25519_MSM_SEGMENT_BUCKET_PASS_TERMS terms, in the same workspace.  tools/seg_msm_numbers.py times the call against one
+ * c25519_msm_vartime_dev per segment and against c25519_mul_batch_dev + c25519_point_sum_segments_dev. */
 #define C25519_MSM_SEGMENT_DIRECT_MAX 64       /* longest segment that runs in one lane */
 #define C25519_MSM_SEGMENT_WAVE_MAX 2048       /* longest segment that runs in one wave (measured: DESIGN.md section 3.13) */
 #define C25519_MSM_SEGMENT_PASS_TERMS 262144   /* most terms whose tables are resident at once (2^18: a 352 MB workspace) */
+#define C25519_MSM_SEGMENT_BUCKET_MAX 32768    /* longest segment on the bucket route (measured: DESIGN.md section 3.13; at most 65536, a term index within its segment is 16 bits) */
+/* Most terms of one bucket pass.  Per term: a 160-byte record, 32 digit bytes, 32 two-byte indices and an ok byte = 257 bytes; per segment
+ * (more than 2048 terms each, so at most 511 of them): 32 window sums of 160 bytes and 32 ok bytes = 5152 bytes.  2^20 x 257 + 511 x 5152 =
+ * 272.1 MB, below the 352 MB of a Straus pass, whose place it takes; 2^21 terms would need 539 MB. */
+#define C25519_MSM_SEGMENT_BUCKET_PASS_TERMS 1048576
 int32_t c25519_msm_vartime_segments_dev(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t *d_points, uint64_t n, int in_fmt,
                                         const uint64_t *seg_off /* HOST, m + 1 */, uint64_t m, int out_fmt, uint8_t *d_out /* device, m x (32 | 160) */,
                                         uint8_t *d_ok /* device, m bytes, may be NULL */);
 int32_t c25519_msm_vartime_segments(c25519_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint64_t n, int in_fmt, const uint64_t *seg_off, uint64_t m,
                                     int out_fmt, uint8_t *out, uint8_t *ok);
 /* how c25519_msm_vartime_segments routes these offsets: plan[0] lane segments, [1] wave segments,
- * [2] single-MSM segments, [3] passes, [4] most terms resident in one pass.  Same validation and error as the call (n is seg_off[m]).
- * Host arithmetic: no context, no GPU. */
+ * [2] segments longer than the wave maximum (bucket and single-MSM segments together), [3] passes of the lane and wave segments, [4] most
+ * terms resident in one of those passes.  Same validation and error as the call (n is seg_off[m]).  Host arithmetic: no context, no GPU. */
 int32_t c25519_msm_vartime_segments_plan(const uint64_t *seg_off, uint64_t m, uint64_t plan[5]);
+/* ... and segment by segment: route[s] is one of the four codes.  Same validation and error; host arithmetic. */
+#define C25519_MSM_SEGMENT_ROUTE_LANE   0
+#define C25519_MSM_SEGMENT_ROUTE_WAVE   1
+#define C25519_MSM_SEGMENT_ROUTE_BUCKET 2
+#define C25519_MSM_SEGMENT_ROUTE_SINGLE 3
+int32_t c25519_msm_vartime_segments_routes(const uint64_t *seg_off, uint64_t m, uint8_t *route /* m bytes */);
 
 /* The same decomposition WITHOUT the partial sum ever visiting the host (what curve25519-dalek_amd/multi.py runs, one
  * process per GPU): c25519_msm_partial_record_dev only ENQUEUES on the context's stream and leaves a fixed-size RECORD in

@@ -16,7 +16,11 @@ and 4096 segments (m capped so that m x len <= 2^20), and the pair just below an
 tree without the wave route does for these lengths inside the call, one single-MSM call per segment.  The outputs are compared with route A's
 on the first segments.  A tree whose engine has no MSM_SEGMENT_WAVE_MAX (before the wave route) runs the same rows: run the script on
 both trees on one box in one session, the second time with --append, to see what the route changed.
-    python tools/seg_msm_numbers.py [--root TREE] [--label TEXT] [--append] [--out FILE]
+The bucket route (more than WAVE_MAX and at most C25519_MSM_SEGMENT_BUCKET_MAX terms, every such segment of a call side by side): segments x
+terms of 8 / 64 / 512 x 2049, 64 / 1024 x 4096, 64 x 8192, 64 / 256 x 16384, 64 x 32768, 16 / 64 x 65536, and one lone segment of each length;
+median of 5 repeats.  A tree before the bucket route runs the same rows on its single-MSM route: `--section long` runs these rows alone, for
+the two runs on one box in one session.
+    python tools/seg_msm_numbers.py [--root TREE] [--label TEXT] [--append] [--out FILE] [--section all|long]
 (writes profiles/seg_msm_numbers.txt of this tree, or FILE, and prints it; --root: import the package from another checkout, built there)"""
 import argparse
 import os
@@ -29,6 +33,7 @@ ap.add_argument("--root", default=ROOT, help="the checkout whose package and lib
 ap.add_argument("--label", default="", help="a line that names the tree in the output")
 ap.add_argument("--append", action="store_true", help="append to the output file instead of replacing it")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "seg_msm_numbers.txt"))
+ap.add_argument("--section", default="all", choices=("all", "long"), help="long: only the rows of the bucket route's lengths")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.root))
 import numpy as np
@@ -58,11 +63,11 @@ def warm():
         e.microbench(0, 4000)
 
 
-def timed(f):
+def timed(f, reps=None):
     """-> (median, min, max) ms over REPS runs of f, events on the stream, after one warm-up run"""
     warm(); f()
     ts = []
-    for _ in range(REPS):
+    for _ in range(reps or REPS):
         t0 = torch.cuda.Event(enable_timing=True); t1 = torch.cuda.Event(enable_timing=True)
         t0.record(); f(); t1.record(); t1.synchronize()
         ts.append(t0.elapsed_time(t1))
@@ -104,26 +109,26 @@ def verdict(new, other):
     return "new x%.1f" % (other[0] / new[0]) if new[0] < other[0] else "NEW LOSES x%.1f" % (new[0] / other[0])
 
 
-def case(name, lengths, with_a=True, with_b=True, check_a=0):
+def case(name, lengths, with_a=True, with_b=True, check_a=0, reps=None):
     lengths = np.asarray(lengths, dtype=np.int64)
     m, n = len(lengths), int(lengths.sum())
     off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
     off_dev = torch.from_numpy(off.astype(np.int64)).cuda()
     s, pts = inputs(n)
     res = {}
-    new = timed(lambda: res.__setitem__("new", e.msm_vartime_segments_t(s, pts, off, RAW, ED)))
+    new = timed(lambda: res.__setitem__("new", e.msm_vartime_segments_t(s, pts, off, RAW, ED)), reps)
     assert res["new"][0] == 0
     row = "%-26s m %7d n %8d | new %s" % (name, m, n, fmt(new))
     if with_a:
         cnt = min(m, A_SAMPLE)
-        a = timed(lambda: route_a(s, pts, off, cnt))
+        a = timed(lambda: route_a(s, pts, off, cnt), reps)
         a = tuple(x * m / cnt for x in a)
         row += " | A %s %-16s" % (fmt(a), verdict(new, a))
-        if check_a:                                          # the first check_a sums against the single call's, byte for byte
-            keep = []
-            route_a(s, pts, off, min(m, check_a), keep)
-            got = res["new"][1][:len(keep)].cpu().numpy()
-            assert [bytes(got[k]) for k in range(len(keep))] == keep, "the new call and route A disagree at %s" % name
+    if check_a:                                              # the first check_a sums against the single call's, byte for byte (also without route A's timing)
+        keep = []
+        route_a(s, pts, off, min(m, check_a), keep)
+        got = res["new"][1][:len(keep)].cpu().numpy()
+        assert [bytes(got[k]) for k in range(len(keep))] == keep, "the new call and route A disagree at %s" % name
     if with_b:
         def fb():
             prod, _ = ev.mul_batch_t(s, pts, RAW, RAW)
@@ -140,6 +145,24 @@ if args.label:
 out("multiplier probe (Engine.microbench(0, 4000), best of 100): %.1f Top/s" % (max(e.microbench(0, 4000) for _ in range(100)) / 1e3))
 out("segmented vartime MSM, ms per call: median (min .. max) of %d repeats; DIRECT_MAX %d, WAVE_MAX %s, PASS_TERMS %d; route A scaled from its first %d segments"
     % (REPS, L, W if HAS_WAVE else "none (no wave route in this tree)", T, A_SAMPLE))
+
+
+def long_section():
+    bmax = getattr(pkg.engine, "MSM_SEGMENT_BUCKET_MAX", None)
+    out("-- the bucket route: more than WAVE_MAX and at most BUCKET_MAX (%s) terms; median of 5 repeats; route A where m <= 64"
+        % (bmax if bmax else "none: no bucket route in this tree, every row is one single-MSM call per segment inside the call"))
+    for m, ln in ((8, 2049), (64, 2049), (512, 2049), (64, 4096), (1024, 4096), (64, 8192), (64, 16384), (256, 16384), (64, 32768), (16, 65536), (64, 65536)):
+        case("%d x %d" % (m, ln), [ln] * m, with_a=m <= 64, with_b=False, check_a=2, reps=5)
+    for ln in (2049, 4096, 16384, 65536):
+        case("1 x %d" % ln, [ln], with_b=False, check_a=1, reps=5)
+
+
+if args.section == "long":
+    long_section()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "a" if args.append else "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    sys.exit(0)
 N = 1 << 18
 for ln in (2, 4, 16, 64):
     case("len %d" % ln, [ln] * (N // ln))
@@ -158,6 +181,7 @@ out("-- around C25519_MSM_SEGMENT_WAVE_MAX: one wave against one single-MSM call
 for m in (64, (1 << 20) // (W + 1)):
     case("len %d (wave)" % W, [W] * m, with_b=False, check_a=2)
     case("len %d (single-MSM route)" % (W + 1), [W + 1] * m, with_b=False, check_a=2)
+long_section()
 out("-- passes: 2^20 terms are four passes of C25519_MSM_SEGMENT_PASS_TERMS; per term they should cost what one pass costs")
 one = case("len 4, 2^18 terms", [4] * (N // 4), with_a=False, with_b=False)
 four = case("len 4, 2^20 terms", [4] * N, with_a=False, with_b=False)
