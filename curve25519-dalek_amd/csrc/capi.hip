@@ -402,22 +402,23 @@ int32_t ffi_upload_msgs(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *ms
 int32_t ffi_small_upload(c25519_ctx *ctx, int pieces, const void *const *src, const size_t *bytes, uint8_t **d, size_t min_stage, bool zero_copy) {
     HIPCHK(hipSetDevice(ctx->device));
     ctx->ffi_t0 = wall_ms();
-    size_t off[8], total = 0;
+    size_t off[8];
     if (pieces > 8) return bad_arg(ctx, "ffi_small_upload: too many pieces");
-    for (int i = 0; i < pieces; i++) { off[i] = total; total += (bytes[i] + 255) & ~(size_t)255; }
+    ws_layout S;                                            // the same parts in the staging buffer and in tmp_a
+    for (int i = 0; i < pieces; i++) off[i] = S.part(bytes[i]);
     int32_t r;
     // min_stage: what the rest of the call will ask of the staging buffer (the strict z-mode of verify_batch keeps its host copies there): it must not
     // be re-allocated while the upload below is still reading it
-    if ((r = ctx_host_stage(ctx, std::max(total + 256, min_stage)))) return r;
+    if ((r = ctx_host_stage(ctx, std::max(S.bytes(256), min_stage)))) return r;
     if (zero_copy) {
         uint8_t *dv = nullptr;
         HIPCHK(hipHostGetDevicePointer((void **)&dv, ctx->h_stage, 0));
         for (int i = 0; i < pieces; i++) { if (bytes[i]) memcpy((uint8_t *)ctx->h_stage + off[i], src[i], bytes[i]); d[i] = dv + off[i]; }
         return C25519_OK;
     }
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, total + 256))) return r;
-    for (int i = 0; i < pieces; i++) { if (bytes[i]) memcpy((uint8_t *)ctx->h_stage + off[i], src[i], bytes[i]); d[i] = (uint8_t *)ctx->tmp_a.p + off[i]; }
-    if (total) HIPCHK(hipMemcpyAsync(ctx->tmp_a.p, ctx->h_stage, total, hipMemcpyHostToDevice, ctx->stream));
+    if ((r = S.reserve(ctx, ctx->tmp_a, 256))) return r;
+    for (int i = 0; i < pieces; i++) { if (bytes[i]) memcpy((uint8_t *)ctx->h_stage + off[i], src[i], bytes[i]); d[i] = S.at(off[i]); }
+    if (S.bytes()) HIPCHK(hipMemcpyAsync(ctx->tmp_a.p, ctx->h_stage, S.bytes(), hipMemcpyHostToDevice, ctx->stream));
     return C25519_OK;
 }
 void ffi_small_begin(c25519_ctx *ctx) { ctx->ffi_t0 = wall_ms(); }

@@ -15,6 +15,17 @@
 
 static inline unsigned div_up(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }       // the parts of a carved workspace
+// The parts of ONE devbuf: each a multiple of 256 bytes, one behind the other in the order they are declared.  Declare every part, reserve
+// once, then ask for typed pointers.
+struct ws_layout {
+    size_t off = 0;
+    uint8_t *base = nullptr;
+    size_t part(size_t bytes) { const size_t o = off; off += al256(bytes); return o; }      // -> its offset; a part of 0 bytes takes nothing
+    size_t bytes(size_t slack = 0) const { return off + slack; }
+    void bind(void *p) { base = (uint8_t *)p; }                                              // over memory that is reserved already
+    int32_t reserve(c25519_ctx *ctx, devbuf &b, size_t slack = 0) { const int32_t r = ctx_reserve(ctx, b, bytes(slack)); bind(b.p); return r; }
+    template <class T = uint8_t> T *at(size_t o) const { return (T *)(base + o); }
+};
 
 // a rejected argument: the message for c25519_last_error and the status every entry point returns for it.  (ctx may be null: the *_plan
 // exports have none, and then only the status is returned)

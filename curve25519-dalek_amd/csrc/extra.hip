@@ -418,12 +418,10 @@ EXPORT int32_t ed25519_verify_batch_multi(c25519_ctx **ctxs, int32_t nctx, const
             if ((e = hipSetDevice(c->device)) != hipSuccess) return fail(r, e, "hipSetDevice");
             const uint64_t mlen = msg_off[lo + cnt] - msg_off[lo];
             // tmp_c: sigs 64 cnt | pks 32 cnt | hram 64 cnt + 64 | z 16 cnt | record ;  tmp_a: messages ;  tmp_b: offsets
-            size_t off = 0;
-            auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-            const size_t oS = carve(cnt * 64), oK = carve(cnt * 32), oH = carve(cnt * 64 + 64), oZ = carve(cnt * 16 + 16), oR = carve(C25519_PARTIAL_RECORD_BYTES);
-            if ((st[r] = ctx_reserve(c, c->tmp_c, off)) || (st[r] = ctx_reserve(c, c->tmp_a, mlen + 64)) || (st[r] = ctx_reserve(c, c->tmp_b, (cnt + 1) * 8))) return;
-            uint8_t *ws = (uint8_t *)c->tmp_c.p;
-            dv[r] = shard_dev{ws + oS, ws + oK, ws + oH, ws + oZ, ws + oR};
+            ws_layout W;
+            const size_t oS = W.part(cnt * 64), oK = W.part(cnt * 32), oH = W.part(cnt * 64 + 64), oZ = W.part(cnt * 16 + 16), oR = W.part(C25519_PARTIAL_RECORD_BYTES);
+            if ((st[r] = W.reserve(c, c->tmp_c)) || (st[r] = ctx_reserve(c, c->tmp_a, mlen + 64)) || (st[r] = ctx_reserve(c, c->tmp_b, (cnt + 1) * 8))) return;
+            dv[r] = shard_dev{W.at(oS), W.at(oK), W.at(oH), W.at(oZ), W.at(oR)};
             std::vector<uint64_t> offs(cnt + 1);
             for (uint64_t i = 0; i <= cnt; i++) offs[i] = msg_off[lo + i] - msg_off[lo];
             if (mlen && (e = hipMemcpyAsync(c->tmp_a.p, msgs + msg_off[lo], mlen, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(r, e, "H2D");

@@ -43,6 +43,14 @@ struct ffi_guard {
     ~ffi_guard() { if (armed) (void)ffi_end(ctx, 0, 0); }
 };
 
+// A call that uploads pass by pass: the event behind the copies just queued on the H2D copy stream, from the rotating slots of ev_up (slot: 0 at the call's start)
+static inline int32_t ffi_up_ready(c25519_ctx *ctx, int &slot, hipEvent_t *ready) {
+    *ready = ctx->ev_up[slot];
+    slot = (slot + 1) % c25519_ctx::FFI_MAXCH;
+    const hipError_t e = hipEventRecord(*ready, ctx->s_h2d);
+    return e == hipSuccess ? 0 : c25519_fail(ctx, e, "hipEventRecord(ctx->ev_up[slot], ctx->s_h2d)");
+}
+
 // units per chunk: at most FFI_MAXCH chunks of at least min_units units, a multiple of 1024
 static inline uint64_t ffi_chunk_units(uint64_t n, uint64_t min_units) {
     if (n <= min_units) return n ? n : 1;

@@ -409,18 +409,17 @@ static int32_t sum_enqueue(c25519_ctx *ctx, const uint8_t *d_points, uint64_t n,
     hipStream_t st = ctx->stream;
     // tmp_f: ok (m) | S40 (m x 160) | Sbad (m) | keys of level 0 (n x 4) | two piece buffers of n1 = 2 ceil(n / C) records (P40, key, bad)
     const uint64_t nch0 = (n + SUM_C - 1) / SUM_C, n1 = 2 * nch0;
-    const size_t b_ok = al256(m), b_S = al256(m * 160), b_Sb = al256(m), b_k = al256(n * 4), b_P = al256(n1 * 160) + al256(n1 * 4) + al256(n1);
+    ws_layout F;
+    const size_t o_ok = F.part(m), o_S = F.part(m * 160), o_Sb = F.part(m), o_k = F.part(n * 4);
+    size_t o_P40[2], o_Pkey[2], o_Pbad[2];
+    for (int i = 0; i < 2; i++) { o_P40[i] = F.part(n1 * 160); o_Pkey[i] = F.part(n1 * 4); o_Pbad[i] = F.part(n1); }
     int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, b_ok + b_S + b_Sb + b_k + 2 * b_P + 256))) return r;
-    uint8_t *base = (uint8_t *)ctx->tmp_f.p;
-    uint8_t *okbuf = d_ok ? d_ok : base;
-    u32 *S40 = (u32 *)(base + b_ok);
-    uint8_t *Sbad = base + b_ok + b_S;
-    u32 *keys0 = (u32 *)(base + b_ok + b_S + b_Sb);
-    uint8_t *pb[2] = {base + b_ok + b_S + b_Sb + b_k, base + b_ok + b_S + b_Sb + b_k + b_P};
-    auto P40_of = [&](int i) { return (u32 *)pb[i]; };
-    auto Pkey_of = [&](int i) { return (u32 *)(pb[i] + al256(n1 * 160)); };
-    auto Pbad_of = [&](int i) { return pb[i] + al256(n1 * 160) + al256(n1 * 4); };
+    if ((r = F.reserve(ctx, ctx->tmp_f, 256))) return r;
+    uint8_t *okbuf = d_ok ? d_ok : F.at(o_ok), *Sbad = F.at(o_Sb);
+    u32 *S40 = F.at<u32>(o_S), *keys0 = F.at<u32>(o_k);
+    auto P40_of = [&](int i) { return F.at<u32>(o_P40[i]); };
+    auto Pkey_of = [&](int i) { return F.at<u32>(o_Pkey[i]); };
+    auto Pbad_of = [&](int i) { return F.at(o_Pbad[i]); };
     if (n) {
         hipLaunchKernelGGL(k_seg_keys, dim3(div_up(n, 256)), dim3(256), 0, st, d_seg_off, m, n, keys0);
         const unsigned g0 = div_up(nch0, 4);
@@ -477,11 +476,11 @@ EXPORT int32_t c25519_point_sum_segments(c25519_ctx *ctx, const uint8_t *points,
     for (uint64_t s = 0; s < m; s++)
         if (seg_off[s + 1] < seg_off[s]) return bad_arg(ctx, "point_sum_segments: seg_off must be non-decreasing");
     const size_t pb = point_bytes(in_fmt), ob = point_bytes(out_fmt);
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * pb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, (m + 1) * 8 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, al256(m * ob) + m + 16)))
-        return r;
+    ws_layout O; O.part(m * ob);                            // tmp_c: the sums | their ok bytes (the tail: not rounded, and 16 bytes behind it)
+    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * pb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, (m + 1) * 8 + 16)) || (r = O.reserve(ctx, ctx->tmp_c, m + 16))) return r;
     ffi_small_begin(ctx);
     hipStream_t st = ctx->stream;
-    uint8_t *d_sums = (uint8_t *)ctx->tmp_c.p, *d_ok = d_sums + al256(m * ob);
+    uint8_t *d_sums = O.at(0), *d_ok = O.at(O.bytes());
     if (grp_compressed(in_fmt)) HIPCHK(hipMemsetAsync(ctx->d_flag, 0, 4, st));
     if (n) HIPCHK(hipMemcpyAsync(ctx->tmp_a.p, points, n * pb, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ctx->tmp_b.p, seg_off, (m + 1) * 8, hipMemcpyHostToDevice, st));

@@ -371,22 +371,20 @@ int32_t msm_mid_enqueue(c25519_ctx *ctx, const msm_call &call, const uint8_t *d_
     const uint64_t entries = (uint64_t)g.nwin * n;
     const uint32_t max_long = (uint32_t)std::min<uint64_t>(nb, entries / g.long_cap + 1);
     const uint32_t max_items = (uint32_t)(entries / MID_LONG_SEG + max_long + 1);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t oD = carve((size_t)g.nwin * dstride * 2), oB = carve((size_t)g.nwin * (g.half + 1) * 4), oS = carve((size_t)g.nwin * n * 4), oK = carve(nb * 160), oPerm = carve(nb * 4), oT = carve(nb * 4);
-    const size_t oSW = carve((size_t)g.nwin * nseg * 2 * 160), oLI = carve((size_t)max_items * sizeof(mid_item)), oLG = carve((size_t)max_long * 4), oLS = carve((size_t)max_items * 160);
-    const size_t oBF = carve((size_t)nfront * 4);
+    ws_layout W;
+    const size_t oD = W.part((size_t)g.nwin * dstride * 2), oB = W.part((size_t)g.nwin * (g.half + 1) * 4), oS = W.part((size_t)g.nwin * n * 4), oK = W.part(nb * 160), oPerm = W.part(nb * 4), oT = W.part(nb * 4);
+    const size_t oSW = W.part((size_t)g.nwin * nseg * 2 * 160), oLI = W.part((size_t)max_items * sizeof(mid_item)), oLG = W.part((size_t)max_long * 4), oLS = W.part((size_t)max_items * 160);
+    const size_t oBF = W.part((size_t)nfront * 4);
     // small words zeroed by k_mid_front: [0] long items, [1] long buckets, [2] finished windows (k_reduce_b4pub), [64 .. 320) the bucket-order histogram, [320 .. 576) its
     // cursors, [576 .. 576 + max_long) finished segments per long bucket
     const int nzero = 576 + (int)max_long;
-    const size_t oZ = carve((size_t)nzero * 4);
+    const size_t oZ = W.part((size_t)nzero * 4);
     int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_d, off))) return r;
-    uint8_t *ws = (uint8_t *)ctx->tmp_d.p;
-    uint16_t *D = (uint16_t *)(ws + oD);
-    uint32_t *base = (uint32_t *)(ws + oB), *sorted = (uint32_t *)(ws + oS), *buckets = (uint32_t *)(ws + oK), *perm = (uint32_t *)(ws + oPerm), *SW = (uint32_t *)(ws + oSW), *totals = (uint32_t *)(ws + oT);
-    mid_item *items = (mid_item *)(ws + oLI);
-    uint32_t *lgids = (uint32_t *)(ws + oLG), *segs = (uint32_t *)(ws + oLS), *blockflags = (uint32_t *)(ws + oBF), *zw = (uint32_t *)(ws + oZ);
+    if ((r = W.reserve(ctx, ctx->tmp_d))) return r;
+    uint16_t *D = W.at<uint16_t>(oD);
+    uint32_t *base = W.at<uint32_t>(oB), *sorted = W.at<uint32_t>(oS), *buckets = W.at<uint32_t>(oK), *perm = W.at<uint32_t>(oPerm), *SW = W.at<uint32_t>(oSW), *totals = W.at<uint32_t>(oT);
+    mid_item *items = W.at<mid_item>(oLI);
+    uint32_t *lgids = W.at<uint32_t>(oLG), *segs = W.at<uint32_t>(oLS), *blockflags = W.at<uint32_t>(oBF), *zw = W.at<uint32_t>(oZ);
     const uint32_t *recs = (const uint32_t *)points;
     // raw points: up to MID_PROJ_MAX terms the records are PROJECTIVE (no inversion; 8 M additions in k_mid_acc_long); above, the batched normaliser (msm.hip
     // k_prep_raw2) makes affine records on this stream WHILE the digits and the sort run on the second one, and the accumulation is the bucket pipeline's

@@ -203,11 +203,12 @@ static int32_t fold_run(c25519_ctx *ctx, const c25519_precomp *p, const uint8_t 
     hipStream_t st = ctx->stream;
     const fold_geom g = fold_geometry(m, w);
     // tmp_f: dyn_off (m + 1) | partial column sums (slices x w; none with one slice) | t (w) | d' (n_dyn); none of the MSM paths touches tmp_f
-    const size_t b_off = al256((m + 1) * 8), b_part = g.slices > 1 ? al256(g.slices * w * 32) : 0, b_t = al256(w * 32), b_d = al256(n_dyn * 32);
+    ws_layout F;
+    const size_t o_off = F.part((m + 1) * 8), o_part = F.part(g.slices > 1 ? g.slices * w * 32 : 0), o_t = F.part(w * 32), o_d = F.part(n_dyn * 32);
     int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, b_off + b_part + b_t + b_d + 256))) return r;
-    uint8_t *base = (uint8_t *)ctx->tmp_f.p, *d_part = base + b_off, *d_t = d_part + b_part, *d_dd = d_t + b_t;
-    uint64_t *d_off = (uint64_t *)base;
+    if ((r = F.reserve(ctx, ctx->tmp_f, 256))) return r;
+    uint8_t *d_part = F.at(o_part), *d_t = F.at(o_t), *d_dd = F.at(o_d);
+    uint64_t *d_off = F.at<uint64_t>(o_off);
     const uint64_t call = ctx->ncalls;
     hipEvent_t *ring = ctx_ring_item(ctx);
     ctx->last_passes.clear();
@@ -266,10 +267,11 @@ EXPORT int32_t c25519_precomp_msm_vartime_mixed_rows_fold(c25519_ctx *ctx, const
     if ((r = fold_check(ctx, p, m, w, n_dyn, in_fmt, dyn_off, weight_bytes, out_fmt))) return r;
     if (m == 0) { host_encode(ge_identity(), out_fmt, out); return C25519_OK; }
     // tmp_a: static scalars | weights; tmp_b: dynamic scalars; tmp_c: dynamic points (the staging buffers of a host form; the MSM keeps to its own)
-    const size_t pb = point_bytes(in_fmt), sb = al256((size_t)(m * w) * 32), wb = (size_t)m * (size_t)weight_bytes;
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, sb + wb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n_dyn * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, n_dyn * pb + 16))) return r;
+    const size_t pb = point_bytes(in_fmt), wb = (size_t)m * (size_t)weight_bytes;
+    ws_layout A; A.part((size_t)(m * w) * 32);              // (the weights are the tail: not rounded, and 16 bytes behind it)
+    if ((r = A.reserve(ctx, ctx->tmp_a, wb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n_dyn * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, n_dyn * pb + 16))) return r;
     ffi_small_begin(ctx);
-    uint8_t *d_ss = (uint8_t *)ctx->tmp_a.p, *d_wts = d_ss + sb, *d_ds = (uint8_t *)ctx->tmp_b.p, *d_dp = (uint8_t *)ctx->tmp_c.p;
+    uint8_t *d_ss = A.at(0), *d_wts = A.at(A.bytes()), *d_ds = (uint8_t *)ctx->tmp_b.p, *d_dp = (uint8_t *)ctx->tmp_c.p;
     const struct { void *dst; const void *src; size_t bytes; } ups[4] = {{d_ss, static_scalars, (size_t)(m * w) * 32}, {d_wts, weights, wb}, {d_ds, dyn_scalars, n_dyn * 32},
                                                                          {d_dp, dyn_points, n_dyn * pb}};
     for (const auto &u : ups) {

@@ -183,7 +183,7 @@ static int32_t mixed_run(c25519_ctx *ctx, c25519_precomp *p, const uint8_t *d_ss
         HIPCHK(hipEventRecord(ctx->ev0, st));
         if ((r = ctx_reserve(ctx, ctx->tmp_f, ws.bytes()))) return r;
         if ((r = rows_build(ctx, p))) return r;
-        ws.carve((uint8_t *)ctx->tmp_f.p, d_out, d_ok);
+        ws.bind(ctx->tmp_f.p, d_out, d_ok);
         HIPCHK(hipMemsetAsync(flags, 0, 8, st));
         HIPCHK(hipMemcpyAsync(ws.d_off, dyn_off, (m + 1) * 8, hipMemcpyHostToDevice, st));
         ctx->kname[0] = route == C25519_PRECOMP_ROWS_LANE ? "c25519::k_mid_mixed_lane (one lane per row: its dynamic terms by Straus, then its static scalars over the comb table)"
@@ -225,11 +225,12 @@ EXPORT int32_t c25519_precomp_msm_vartime_mixed_rows(c25519_ctx *ctx, c25519_pre
     if ((r = mixed_check(ctx, p, m, w, n_dyn, in_fmt, dyn_off, route, out_fmt, R))) return r;
     if (m == 0) return C25519_OK;
     const size_t pb = point_bytes(in_fmt), ob = point_bytes(out_fmt), sb = (size_t)(m * w) * 32;       // (w <= 4096 and m < 2^32: no overflow)
+    ws_layout O; O.part(m * ob);                            // tmp_d: the sums | their ok bytes (the tail: not rounded, and 16 bytes behind it)
     if ((r = ctx_reserve(ctx, ctx->tmp_a, sb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n_dyn * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, n_dyn * pb + 16)) ||
-        (r = ctx_reserve(ctx, ctx->tmp_d, al256(m * ob) + m + 16)))
+        (r = O.reserve(ctx, ctx->tmp_d, m + 16)))
         return r;
     ffi_small_begin(ctx);
-    uint8_t *d_ss = (uint8_t *)ctx->tmp_a.p, *d_ds = (uint8_t *)ctx->tmp_b.p, *d_dp = (uint8_t *)ctx->tmp_c.p, *d_out = (uint8_t *)ctx->tmp_d.p, *d_ok = d_out + al256(m * ob);
+    uint8_t *d_ss = (uint8_t *)ctx->tmp_a.p, *d_ds = (uint8_t *)ctx->tmp_b.p, *d_dp = (uint8_t *)ctx->tmp_c.p, *d_out = O.at(0), *d_ok = O.at(O.bytes());
     if ((r = straus_upload_all(ctx, {{d_ss, static_scalars, sb}, {d_ds, dyn_scalars, n_dyn * 32}, {d_dp, dyn_points, n_dyn * pb}}))) return r;
     r = mixed_run(ctx, p, d_ss, m, w, d_ds, d_dp, in_fmt, dyn_off, R, route == C25519_PRECOMP_ROWS_AUTO ? R.route : route, out_fmt, d_out, d_ok, out, ok);
     if (r < 0) (void)hipStreamSynchronize(ctx->stream);    // (an early error: the uploads may still be reading the caller's memory)

@@ -216,11 +216,12 @@ static int32_t seg_run(c25519_ctx *ctx, const uint8_t *d_scalars, const uint8_t 
         for (uint64_t k = p.k0; k < p.k1; k++) bdesc.push_back(R.buckets[k]);
     }
     segb_ws bw(R.bmaxt, R.bmaxseg, bdesc.size());
-    const size_t ws_head = ws.b_off + ws.b_ids + ws.b_sum + ws.b_ok, ws_pass = std::max(ws.b_tab + ws.b_dig + ws.b_tok, bw.pass_bytes());
+    ws_layout F;
+    const size_t o_head = F.part(ws.head_bytes()), o_pass = F.part(std::max(ws.pass_bytes(), bw.pass_bytes())), o_desc = F.part(bw.b_desc);
     int32_t r;
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, ws_head + ws_pass + bw.b_desc + 256))) return r;
-    ws.carve((uint8_t *)ctx->tmp_f.p, d_out, d_ok);
-    bw.carve((uint8_t *)ctx->tmp_f.p + ws_head, (uint8_t *)ctx->tmp_f.p + ws_head + ws_pass);
+    if ((r = F.reserve(ctx, ctx->tmp_f, 256))) return r;
+    ws.bind(F.at(o_head), d_out, d_ok);
+    bw.bind(F.at(o_pass), F.at(o_desc));
     uint32_t *flags = (uint32_t *)ctx->d_flag;
     auto enqueue = [&]() -> int32_t {
         HIPCHK(hipMemsetAsync(flags, 0, 8, st));
@@ -281,10 +282,10 @@ EXPORT int32_t c25519_msm_vartime_segments(c25519_ctx *ctx, const uint8_t *scala
     if ((r = seg_check(ctx, n, in_fmt, seg_off, m, out_fmt))) return r;
     if (m == 0) return C25519_OK;
     const size_t pb = point_bytes(in_fmt), ob = point_bytes(out_fmt);
-    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * pb + 16)) || (r = ctx_reserve(ctx, ctx->tmp_c, al256(m * ob) + m + 16)))
-        return r;
+    ws_layout O; O.part(m * ob);                            // tmp_c: the sums | their ok bytes (the tail: not rounded, and 16 bytes behind it)
+    if ((r = ctx_reserve(ctx, ctx->tmp_a, n * 32 + 16)) || (r = ctx_reserve(ctx, ctx->tmp_b, n * pb + 16)) || (r = O.reserve(ctx, ctx->tmp_c, m + 16))) return r;
     ffi_small_begin(ctx);
-    uint8_t *d_s = (uint8_t *)ctx->tmp_a.p, *d_p = (uint8_t *)ctx->tmp_b.p, *d_out = (uint8_t *)ctx->tmp_c.p, *d_ok = d_out + al256(m * ob);
+    uint8_t *d_s = (uint8_t *)ctx->tmp_a.p, *d_p = (uint8_t *)ctx->tmp_b.p, *d_out = O.at(0), *d_ok = O.at(O.bytes());
     if ((r = straus_upload_all(ctx, {{d_s, scalars, n * 32}, {d_p, points, n * pb}}))) return r;
     r = seg_run(ctx, d_s, d_p, n, in_fmt, seg_off, m, out_fmt, d_out, d_ok, out, ok);
     if (r < 0) (void)hipStreamSynchronize(ctx->stream);    // (an early error: the uploads may still be reading the caller's memory)

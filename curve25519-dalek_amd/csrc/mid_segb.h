@@ -29,23 +29,20 @@ static inline size_t segb_desc_words(uint64_t nb) { return (size_t)(3 * nb + 1);
 //   window sums (32 x 160 per segment) | window ok bytes (32 per segment)
 // and, for the whole call, the descriptors of all bucket passes.  Every part a multiple of 256 bytes.
 struct segb_ws {
-    size_t b_rec, b_dig, b_idx, b_tok, b_wsum, b_wok, b_desc;
+    ws_layout L;                                            // the parts of a pass
+    size_t o_rec, o_dig, o_idx, o_tok, o_wsum, o_wok, b_desc;
     uint4 *rec = nullptr;
     uint8_t *dig = nullptr, *tok = nullptr, *wok = nullptr;
     uint16_t *idx = nullptr;
     uint32_t *wsum = nullptr;
     uint64_t *desc = nullptr;
     segb_ws(uint64_t maxt, uint64_t maxseg, size_t desc_words)
-        : b_rec(al256(maxt * 160)), b_dig(al256(maxt * c25519::SEGB_WIN)), b_idx(al256(maxt * c25519::SEGB_WIN * 2)), b_tok(al256(maxt)),
-          b_wsum(al256(maxseg * c25519::SEGB_WIN * 160)), b_wok(al256(maxseg * c25519::SEGB_WIN)), b_desc(al256(desc_words * 8)) {}
-    size_t pass_bytes() const { return b_rec + b_dig + b_idx + b_tok + b_wsum + b_wok; }
-    void carve(uint8_t *pass_base, uint8_t *desc_base) {
-        rec = (uint4 *)pass_base;
-        dig = pass_base + b_rec;
-        idx = (uint16_t *)(dig + b_dig);
-        tok = (uint8_t *)idx + b_idx;
-        wsum = (uint32_t *)(tok + b_tok);
-        wok = (uint8_t *)wsum + b_wsum;
+        : o_rec(L.part(maxt * 160)), o_dig(L.part(maxt * c25519::SEGB_WIN)), o_idx(L.part(maxt * c25519::SEGB_WIN * 2)), o_tok(L.part(maxt)),
+          o_wsum(L.part(maxseg * c25519::SEGB_WIN * 160)), o_wok(L.part(maxseg * c25519::SEGB_WIN)), b_desc(al256(desc_words * 8)) {}
+    size_t pass_bytes() const { return L.bytes(); }
+    void bind(void *pass_base, void *desc_base) {
+        L.bind(pass_base);
+        rec = L.at<uint4>(o_rec); dig = L.at(o_dig); idx = L.at<uint16_t>(o_idx); tok = L.at(o_tok); wsum = L.at<uint32_t>(o_wsum); wok = L.at(o_wok);
         desc = (uint64_t *)desc_base;
     }
 };

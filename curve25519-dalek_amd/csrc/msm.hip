@@ -1312,11 +1312,8 @@ EXPORT int32_t c25519_msm_vartime(c25519_ctx *ctx, const uint8_t *scalars, const
     const msm_fetch fetch = [&](uint64_t lo, uint64_t m, hipEvent_t *ready) -> int32_t {
         HIPCHK(hipMemcpyAsync(d_s + lo * 32, scalars + lo * 32, m * 32, hipMemcpyHostToDevice, ctx->s_h2d));
         HIPCHK(hipMemcpyAsync(d_p + lo * psz, points + lo * psz, m * psz, hipMemcpyHostToDevice, ctx->s_h2d));
-        HIPCHK(hipEventRecord(ctx->ev_up[slot], ctx->s_h2d));
-        *ready = ctx->ev_up[slot];
-        slot = (slot + 1) % c25519_ctx::FFI_MAXCH;
         up += m * (32 + psz);
-        return C25519_OK;
+        return ffi_up_ready(ctx, slot, ready);
     };
     ge_p3 R;
     uint32_t flags[8];

@@ -418,17 +418,16 @@ int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_s
     const uint64_t nb = (uint64_t)g.nwin * g.half;
     const int nseg = red_nseg(g.half);
     // workspace carve-up (tmp_d): [digit matrix | counts] (merged layout only) | base | sorted | buckets | segment pairs | flags | perm | long-bucket lists | sort scratch
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t oD = carve(matrix ? (size_t)g.nwin * nc * 2 : 0), oC = carve(matrix ? (size_t)g.nwin * nchunk * g.half * 4 : 0), oB = carve((size_t)g.nwin * (g.half + 1) * 4);
-    const size_t oS = carve((size_t)g.nwin * nc * 4), oK = carve(nb * 160), oT = carve(nb * 4);
-    const size_t oSW = carve((size_t)g.nwin * nseg * 2 * 160), oF = carve(16384), oPerm = carve(nb * 4);
+    ws_layout W;
+    const size_t oD = W.part(matrix ? (size_t)g.nwin * nc * 2 : 0), oC = W.part(matrix ? (size_t)g.nwin * nchunk * g.half * 4 : 0), oB = W.part((size_t)g.nwin * (g.half + 1) * 4);
+    const size_t oS = W.part((size_t)g.nwin * nc * 4), oK = W.part(nb * 160), oT = W.part(nb * 4);
+    const size_t oSW = W.part((size_t)g.nwin * nseg * 2 * 160), oF = W.part(16384), oPerm = W.part(nb * 4);
     // long-bucket path: at most (#entries / LONG_SEG + #long buckets) work items; a long bucket has > LONG_CAP entries
     const uint64_t entries = (uint64_t)g.nwin * nc;
     const uint32_t max_long = (uint32_t)std::min<uint64_t>(nb, entries / g.long_cap + 1);
     const uint32_t max_items = (uint32_t)(entries / LONG_SEG + max_long + 1);
-    const size_t oLI = carve((size_t)max_items * sizeof(long_item)), oLG = carve((size_t)max_long * 4), oLF = carve((size_t)max_long * 4);
-    const size_t oLS = carve((size_t)max_items * 160);
+    const size_t oLI = W.part((size_t)max_items * sizeof(long_item)), oLG = W.part((size_t)max_long * 4), oLF = W.part((size_t)max_long * 4);
+    const size_t oLS = W.part((size_t)max_items * 160);
     const bool use_part = matrix && g.c >= 13 && n <= (1ull << 23) && n >= (1ull << 16);          // the two-pass partition of the digit-matrix sort
     // (block shapes of the chunk-local sort: 1024-thread blocks, the fastest alone.  256- and 512-thread partition blocks that fit beside a k_accumulate held at
     //  two waves per SIMD were measured and not adopted: profiles/r04_ab_sort_beside_accumulate.txt)
@@ -436,30 +435,29 @@ int32_t msm_enqueue_sort(c25519_ctx *ctx, const uint8_t *d_scalars, uint64_t n_s
     // chunk-local form: P1 holds whole chunk blocks, oCC the slice starts [window][SL + 1][chunk], oBB the bin totals and the chunks' flags
     const size_t p1_words = matrix ? (size_t)g.nwin * nc : (size_t)g.nwin * pchunks_c * SWEEP_CHUNK;
     size_t oP1 = 0, oCC = 0, oBB = 0;
-    if (!matrix || use_part) { oP1 = carve(p1_words * 4); oCC = carve((size_t)g.nwin * (SL + 1) * pchunks_c * 4); oBB = carve((size_t)g.nwin * (SL + 1) * 4 + (size_t)pchunks_c * 4); }
-    int32_t r = ctx_reserve(ctx, ctx->tmp_d, off);
+    if (!matrix || use_part) { oP1 = W.part(p1_words * 4); oCC = W.part((size_t)g.nwin * (SL + 1) * pchunks_c * 4); oBB = W.part((size_t)g.nwin * (SL + 1) * 4 + (size_t)pchunks_c * 4); }
+    int32_t r = W.reserve(ctx, ctx->tmp_d);
     if (r) return r;
-    uint8_t *ws = (uint8_t *)ctx->tmp_d.p;
-    uint32_t *base = (uint32_t *)(ws + oB), *sorted = (uint32_t *)(ws + oS), *buckets = (uint32_t *)(ws + oK);
+    uint32_t *base = W.at<uint32_t>(oB), *sorted = W.at<uint32_t>(oS), *buckets = W.at<uint32_t>(oK);
     // small words of the chain (u32 index): [8..] long-bucket counters, [64..319] bucket-order histogram, [320..575] its cursors,
     // [576] "a scalar has bit 255 set" (ORed into the result slot by the bucket reduction: the sort itself never touches the slot)
-    uint32_t *flags = (uint32_t *)(ws + oF), *totals = (uint32_t *)(ws + oT), *ord_hist = flags + 64, *perm = (uint32_t *)(ws + oPerm);
+    uint32_t *flags = W.at<uint32_t>(oF), *totals = W.at<uint32_t>(oT), *ord_hist = flags + 64, *perm = W.at<uint32_t>(oPerm);
     uint32_t *ord_cursor = flags + 320, *bad_ws = flags + 576;
     constexpr int ZERO_WORDS = 576;                          // zeroed by the partition kernel
     pl.g = g; pl.n = n; pl.nb = nb; pl.nseg = nseg; pl.max_items = max_items; pl.max_long = max_long;
-    pl.base = base; pl.sorted = sorted; pl.buckets = buckets; pl.perm = perm; pl.SW = (uint32_t *)(ws + oSW); pl.counters = flags + 8; pl.bad_ws = bad_ws;
-    pl.items = (long_item *)(ws + oLI); pl.lgids = (uint32_t *)(ws + oLG); pl.lfirst = (uint32_t *)(ws + oLF); pl.segs = (uint32_t *)(ws + oLS);
+    pl.base = base; pl.sorted = sorted; pl.buckets = buckets; pl.perm = perm; pl.SW = W.at<uint32_t>(oSW); pl.counters = flags + 8; pl.bad_ws = bad_ws;
+    pl.items = W.at<long_item>(oLI); pl.lgids = W.at<uint32_t>(oLG); pl.lfirst = W.at<uint32_t>(oLF); pl.segs = W.at<uint32_t>(oLS);
     pl.sort_stream = sort_stream;
     hipStream_t st = sort_stream ? sort_stream : ctx->stream;
     if (matrix) {
         if (lists_free) HIPCHK(hipStreamWaitEvent(st, lists_free, 0));     // (the digit-matrix sort is not split: all of it waits)
         msm_matrix_sort_args a;
         a.d_scalars = d_scalars; a.n_scalars = n_scalars; a.n = n; a.nchunk = nchunk; a.use_part = use_part; a.SL = SL; a.PART_CHUNK = PART_CHUNK; a.pchunks = pchunks;
-        a.D = (uint16_t *)(ws + oD); a.counts = (uint32_t *)(ws + oC); a.P1 = (uint32_t *)(ws + oP1); a.cc = (uint32_t *)(ws + oCC); a.bin_base = (uint32_t *)(ws + oBB);
+        a.D = W.at<uint16_t>(oD); a.counts = W.at<uint32_t>(oC); a.P1 = W.at<uint32_t>(oP1); a.cc = W.at<uint32_t>(oCC); a.bin_base = W.at<uint32_t>(oBB);
         a.flags = flags; a.totals = totals; a.ord_hist = ord_hist;
         return msm_matrix_sort_enqueue(ctx, g, md, pl, a, st);
     }
-    uint32_t *P1 = (uint32_t *)(ws + oP1), *lsg = (uint32_t *)(ws + oCC), *binm = (uint32_t *)(ws + oBB), *bad_blk = binm + (size_t)g.nwin * (SL + 1);
+    uint32_t *P1 = W.at<uint32_t>(oP1), *lsg = W.at<uint32_t>(oCC), *binm = W.at<uint32_t>(oBB), *bad_blk = binm + (size_t)g.nwin * (SL + 1);
     const uint64_t wstride = (uint64_t)pchunks_c * SWEEP_CHUNK;
     const size_t lds1 = ((size_t)2 * SWEEP_WAVES * SL + SL + 1 + SWEEP_CHUNK) * 4;
     const size_t lds2 = ((size_t)3 * PART_BPS_MAX + PART_CAP + 16 * P2G_ITER) * 4;

@@ -510,13 +510,11 @@ static int32_t verify_each_impl(c25519_ctx *ctx, const uint8_t *d_msgs, const ui
     hipStream_t st = ctx->stream;
     int32_t r;
     // tmp_f: hram 64n | k 32n | s 32n | s_ok n | a_ok n | strict n | rcheck 32n | P40 [k](-A) 160n | Q40 [s]B 160n
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    size_t oH = carve(n * 64), oK = carve(n * 32), oS = carve(n * 32), oSo = carve(n), oAo = carve(n), oSt = carve(n), oRc = carve(n * 32), oP = carve(n * 160), oQ = carve(n * 160);
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, off)) || (r = ctx_reserve(ctx, ctx->scratch, n * 128)) || (r = ctx_reserve(ctx, ctx->prefix, n * 48))) return r;
-    uint8_t *ws = (uint8_t *)ctx->tmp_f.p;
-    uint8_t *hram = ws + oH, *kscal = ws + oK, *sscal = ws + oS, *s_ok = ws + oSo, *a_ok = ws + oAo, *sbad = ws + oSt, *rcheck = ws + oRc;
-    uint32_t *P40 = (uint32_t *)(ws + oP), *Q40 = (uint32_t *)(ws + oQ);
+    ws_layout F;
+    const size_t oH = F.part(n * 64), oK = F.part(n * 32), oS = F.part(n * 32), oSo = F.part(n), oAo = F.part(n), oSt = F.part(n), oRc = F.part(n * 32), oP = F.part(n * 160), oQ = F.part(n * 160);
+    if ((r = F.reserve(ctx, ctx->tmp_f)) || (r = ctx_reserve(ctx, ctx->scratch, n * 128)) || (r = ctx_reserve(ctx, ctx->prefix, n * 48))) return r;
+    uint8_t *hram = F.at(oH), *kscal = F.at(oK), *sscal = F.at(oS), *s_ok = F.at(oSo), *a_ok = F.at(oAo), *sbad = F.at(oSt), *rcheck = F.at(oRc);
+    uint32_t *P40 = F.at<uint32_t>(oP), *Q40 = F.at<uint32_t>(oQ);
     hipEvent_t *ring = ctx_ring_item(ctx);
     HIPCHK(hipEventRecord(ctx->ev0, st));
     HIPCHK(hipMemsetAsync(ctx->d_flag, 0, 16, st));
@@ -620,14 +618,12 @@ static int32_t sign_batch_dev_impl(c25519_ctx *ctx, const uint8_t *d_seeds, cons
                                    uint64_t n, uint8_t *d_pks, uint8_t *d_sigs, const uint8_t *d_dom, uint32_t dom_len) {
     if (n == 0) return C25519_OK;
     int32_t r;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    ws_layout F;
     // a || r contiguous (one fixed-base launch over both, sign_body), then the prefixes; then A || R encodings, then the hashes
-    size_t oA = carve(2 * n * 32), oPre = carve(n * 32), oAR = carve(2 * n * 32), oH = carve(n * 64);
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, off))) return r;
-    uint8_t *ws = (uint8_t *)ctx->tmp_f.p;
-    r = sign_body(ctx, d_seeds, d_msgs, d_msg_off, msgs_len, n, d_pks, d_sigs, ws + oA, ws + oPre, ws + oA + n * 32, ws + oAR + n * 32, ws + oH, d_dom, dom_len);
-    hipError_t e = hipMemsetAsync(ws, 0, oAR, ctx->stream);     // wipe secret scalars / nonces / prefixes on EVERY exit path
+    const size_t oA = F.part(2 * n * 32), oPre = F.part(n * 32), oAR = F.part(2 * n * 32), oH = F.part(n * 64);
+    if ((r = F.reserve(ctx, ctx->tmp_f))) return r;
+    r = sign_body(ctx, d_seeds, d_msgs, d_msg_off, msgs_len, n, d_pks, d_sigs, F.at(oA), F.at(oPre), F.at(oA) + n * 32, F.at(oAR) + n * 32, F.at(oH), d_dom, dom_len);
+    hipError_t e = hipMemsetAsync(F.at(oA), 0, oAR, ctx->stream);     // wipe secret scalars / nonces / prefixes on EVERY exit path
     if (r) return r;
     HIPCHK(e);
     uint32_t fl[4] = {0, 0, 0, 0};                              // bad message offsets (k_hram) -> error, like verify_batch

@@ -253,27 +253,27 @@ static inline bool rows_lane_route(uint64_t m, uint64_t w) { return w < C25519_P
 // The workspace of a call with per-term tables, in ctx->tmp_f:
 //   offsets (m + 1) | segment ids of the wave route (n_ids; may be none) | raw sums (compressed output only) | ok (when the caller gave none) |
 //   tables | digits | term ok bytes (maxt terms: the most of one pass)
-// every part a multiple of 256 bytes, and 256 bytes after the last.  Reserve bytes(), then carve() from the buffer as it stands when
-// everything that reserves tmp_f for this call has done so.
+// every part a multiple of 256 bytes, and 256 bytes after the last.  Reserve bytes(), then bind() to the buffer as it stands when
+// everything that reserves tmp_f for this call has done so.  The last three are the parts of a pass: head_bytes() lie before them.
 struct straus_ws {
-    size_t b_off, b_ids, b_sum, b_ok, b_tab, b_dig, b_tok;
+    ws_layout L;
+    size_t o_off, o_ids, o_sum, o_ok, o_tab, o_dig, o_tok;
     uint64_t *d_off = nullptr;
     uint32_t *d_ids = nullptr;
     uint8_t *sums = nullptr, *okbuf = nullptr;
     uint4 *tab = nullptr;
     uint8_t *dig = nullptr, *tok = nullptr;
     straus_ws(uint64_t m, size_t n_ids, uint64_t maxt, int out_fmt, bool caller_ok)
-        : b_off(al256((m + 1) * 8)), b_ids(al256(n_ids * 4)), b_sum(out_fmt == C25519_FMT_RAW160 ? 0 : al256(m * 160)), b_ok(caller_ok ? 0 : al256(m)),
-          b_tab(al256(maxt * c25519::SEG_ENT * c25519::SEG_ENT_Q * 16)), b_dig(al256(maxt * c25519::SEG_DIG)), b_tok(al256(maxt)) {}
-    size_t bytes() const { return b_off + b_ids + b_sum + b_ok + b_tab + b_dig + b_tok + 256; }
-    void carve(uint8_t *base, uint8_t *d_out, uint8_t *d_ok) {
-        d_off = (uint64_t *)base;
-        d_ids = (uint32_t *)(base + b_off);
-        sums = b_sum ? base + b_off + b_ids : d_out;
-        okbuf = d_ok ? d_ok : base + b_off + b_ids + b_sum;
-        tab = (uint4 *)(base + b_off + b_ids + b_sum + b_ok);
-        dig = base + b_off + b_ids + b_sum + b_ok + b_tab;
-        tok = dig + b_dig;
+        : o_off(L.part((m + 1) * 8)), o_ids(L.part(n_ids * 4)), o_sum(L.part(out_fmt == C25519_FMT_RAW160 ? 0 : m * 160)), o_ok(L.part(caller_ok ? 0 : m)),
+          o_tab(L.part(maxt * c25519::SEG_ENT * c25519::SEG_ENT_Q * 16)), o_dig(L.part(maxt * c25519::SEG_DIG)), o_tok(L.part(maxt)) {}
+    size_t head_bytes() const { return o_tab; }
+    size_t pass_bytes() const { return L.bytes() - o_tab; }
+    size_t bytes() const { return L.bytes(256); }
+    void bind(void *base, uint8_t *d_out, uint8_t *d_ok) {
+        L.bind(base);
+        d_off = L.at<uint64_t>(o_off); d_ids = L.at<uint32_t>(o_ids); tab = L.at<uint4>(o_tab); dig = L.at(o_dig); tok = L.at(o_tok);
+        sums = o_ok != o_sum ? L.at(o_sum) : d_out;          // (no raw sums of its own: the RAW160 output is where they go)
+        okbuf = d_ok ? d_ok : L.at(o_ok);
     }
 };
 

@@ -325,7 +325,8 @@ void ztree_make_ivs(uint64_t n, ztree_ivs &ivs) {
     }
 }
 // the z_i of one pass (n signatures) by the device derivation; z16: room for 4 * ceil(n/4) entries.  t0 / t1: tree scratch
-// ((n/4 + 1) * 32 bytes each).  Enqueued on `sa`.
+// ((n/4 + 1) * 32 bytes each).  Enqueued on `sa`.  What every caller sets aside for it: the hashes, the z_i, each tree buffer, h_i mod l.
+struct zchain_bytes { size_t hram, z16, tree, hred; explicit zchain_bytes(uint64_t n) : hram(n * 64), z16((n + 4) * 16), tree((n / 4 + 2) * 32), hred(n * 32) {} };
 static int32_t zchain_enqueue(c25519_ctx *ctx, hipStream_t sa, const uint8_t *hred, const uint8_t *d_sigs, uint64_t n, uint8_t *t0, uint8_t *t1, uint8_t *z16) {
     ztree_ivs ivs;
     ztree_make_ivs(n, ivs);
@@ -440,14 +441,13 @@ static int32_t verify_pass_enqueue(c25519_ctx *owner, c25519_ctx *ctx, const msm
     if ((r = ctx_reserve(ctx, ctx->tmp_e, verify_pts_bytes(n)))) return r;
     // tmp_f: hram (64n) | z16 (16n) | msm scalars (32m) | tree scratch | partial sums
     const unsigned nblk = div_up64(n, 256);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    size_t oH = carve(n * 64), oZ = carve((n + 4) * 16), oSc = carve((m + 1) * 32), oT0 = carve((n / 4 + 2) * 32), oT1 = carve((n / 4 + 2) * 32), oP = carve((size_t)nblk * 40);
-    const size_t oHr = carve(d_z_pre ? 0 : n * 32);       // h_i mod l, for the device z-tree
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, off))) return r;
-    uint8_t *ws = (uint8_t *)ctx->tmp_f.p;
-    uint8_t *hram = ws + oH, *z16 = ws + oZ, *msc = ws + oSc, *t0 = ws + oT0, *t1 = ws + oT1, *hred = d_z_pre ? nullptr : ws + oHr;
-    uint32_t *partial = (uint32_t *)(ws + oP);
+    const zchain_bytes zc(n);
+    ws_layout F;
+    const size_t oH = F.part(zc.hram), oZ = F.part(zc.z16), oSc = F.part((m + 1) * 32), oT0 = F.part(zc.tree), oT1 = F.part(zc.tree), oP = F.part((size_t)nblk * 40);
+    const size_t oHr = F.part(d_z_pre ? 0 : zc.hred);     // h_i mod l, for the device z-tree
+    if ((r = F.reserve(ctx, ctx->tmp_f))) return r;
+    uint8_t *hram = F.at(oH), *z16 = F.at(oZ), *msc = F.at(oSc), *t0 = F.at(oT0), *t1 = F.at(oT1), *hred = d_z_pre ? nullptr : F.at(oHr);
+    uint32_t *partial = F.at<uint32_t>(oP);
     uint32_t *d_pts = (uint32_t *)ctx->tmp_e.p;
     uint32_t *d_cnt = slot_flags(d_slot);             // [2] bad A, [3] bad R, [4] bad s, [5] bad offsets
     hipEvent_t *ring = pass_ring(owner, ctx, 2);
@@ -816,12 +816,12 @@ static bool verify_small_host_ok(uint64_t n, uint32_t z_mode, msm_geom &g) {
 static int32_t verify_batch_small_host(c25519_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, const uint8_t *sigs, const uint8_t *pks, const uint8_t *pk_points, uint64_t n,
                                        uint32_t z_mode, const msm_geom &g) {
     const uint64_t m = 2 * n + 1;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t oS = 0, oK = al(n * 64), oC = oK + al(n * 32), oH = oC + al(m * 32), oZ = oH + al(n * 64), oP = oZ + al((n + 4) * 16 + n * 32), total = oP + (pk_points ? al(n * 160) : 0);
+    ws_layout H;                                            // (the page-locked staging buffer, read in place by the kernels: not a devbuf)
+    const size_t oS = H.part(n * 64), oK = H.part(n * 32), oC = H.part(m * 32), oH = H.part(n * 64), oZ = H.part((n + 4) * 16 + n * 32), oP = H.part(pk_points ? n * 160 : 0);
     int32_t r;
     ctx->host_us[0] = wall_us();
     ffi_small_begin(ctx);
-    if ((r = ctx_host_stage(ctx, total + 256)) || (r = ctx_reserve(ctx, ctx->tmp_e, m * PTS_BYTES + 256))) return r;
+    if ((r = ctx_host_stage(ctx, H.bytes(256))) || (r = ctx_reserve(ctx, ctx->tmp_e, m * PTS_BYTES + 256))) return r;
     uint8_t *hs = (uint8_t *)ctx->h_stage, *dv = nullptr;
     HIPCHK(hipHostGetDevicePointer((void **)&dv, hs, 0));
     memcpy(hs + oS, sigs, n * 64);
@@ -960,10 +960,7 @@ EXPORT int32_t ed25519_verify_batch_keys(c25519_ctx *ctx, const uint8_t *msgs, c
                 HIPCHK(hipMemcpyAsync(d_off + lo, msg_off + lo, (m + 1) * 8, hipMemcpyHostToDevice, ctx->s_h2d));
                 up += (b1 - b0) + (m + 1) * 8;
             } else { HIPCHK(hipMemcpyAsync(d_pp + lo * 160, pk_points + lo * 160, m * 160, hipMemcpyHostToDevice, ctx->s_h2d)); up += m * 160; }
-            HIPCHK(hipEventRecord(ctx->ev_up[slot], ctx->s_h2d));
-            *ready = ctx->ev_up[slot];
-            slot = (slot + 1) % c25519_ctx::FFI_MAXCH;
-            return C25519_OK;
+            return ffi_up_ready(ctx, slot, ready);
         };
         r = verify_batch_impl(ctx, d_msg, d_off, mlen, d_sig, d_pk, d_pp, n, z_mode, &fetch);
     }
@@ -1002,27 +999,26 @@ EXPORT int32_t c25519_debug_batch_zs(c25519_ctx *ctx, const uint8_t *msgs, const
     }
     const uint64_t mlen = msg_off[n];
     int32_t r;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    size_t oM = carve(mlen + 64), oO = carve((n + 1) * 8), oS = carve(n * 64), oK = carve(n * 32), oH = carve(n * 64), oZ = carve((n + 4) * 16), oT0 = carve((n / 4 + 2) * 32), oT1 = carve((n / 4 + 2) * 32);
-    const size_t oHr = carve(n * 32);
-    if ((r = ctx_reserve(ctx, ctx->tmp_f, off))) return r;
-    uint8_t *ws = (uint8_t *)ctx->tmp_f.p;
+    const zchain_bytes zc(n);
+    ws_layout F;                                            // tmp_f: messages | offsets | signatures | keys | hram | z16 | tree scratch (two) | h_i mod l
+    const size_t oM = F.part(mlen + 64), oO = F.part((n + 1) * 8), oS = F.part(n * 64), oK = F.part(n * 32), oH = F.part(zc.hram), oZ = F.part(zc.z16), oT0 = F.part(zc.tree), oT1 = F.part(zc.tree);
+    const size_t oHr = F.part(zc.hred);
+    if ((r = F.reserve(ctx, ctx->tmp_f))) return r;
     hipStream_t st = ctx->stream;
-    if (mlen) HIPCHK(hipMemcpyAsync(ws + oM, msgs, mlen, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ws + oO, msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ws + oS, sigs, n * 64, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(ws + oK, pks, n * 32, hipMemcpyHostToDevice, st));
+    if (mlen) HIPCHK(hipMemcpyAsync(F.at(oM), msgs, mlen, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(F.at(oO), msg_off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(F.at(oS), sigs, n * 64, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(F.at(oK), pks, n * 32, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(ctx->d_flag, 0, 16, st));
-    HIPCHK(launch_hram(ws + oM, (const uint64_t *)(ws + oO), mlen, ws + oS, ws + oK, n, ws + oH, (uint32_t *)ctx->d_flag, st));
+    HIPCHK(launch_hram(F.at(oM), F.at<const uint64_t>(oO), mlen, F.at(oS), F.at(oK), n, F.at(oH), (uint32_t *)ctx->d_flag, st));
     if (z_mode == C25519_Z_DEVICE) {
-        hipLaunchKernelGGL(k_hram_mod_l, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws + oH, n, ws + oHr);
-        if ((r = zchain_enqueue(ctx, st, ws + oHr, ws + oS, n, ws + oT0, ws + oT1, ws + oZ))) return r;
-        HIPCHK(hipMemcpyAsync(out_z16, ws + oZ, n * 16, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_hram_mod_l, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, F.at(oH), n, F.at(oHr));
+        if ((r = zchain_enqueue(ctx, st, F.at(oHr), F.at(oS), n, F.at(oT0), F.at(oT1), F.at(oZ)))) return r;
+        HIPCHK(hipMemcpyAsync(out_z16, F.at(oZ), n * 16, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     } else {
         std::vector<uint8_t> hh(n * 64);
-        HIPCHK(hipMemcpyAsync(hh.data(), ws + oH, n * 64, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(hh.data(), F.at(oH), n * 64, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         c25519_transcript_zs(hh.data(), sigs, n, out_z16);
     }

@@ -433,22 +433,18 @@ static int32_t vseg_run(c25519_ctx *ctx, const uint8_t *d_msgs, const uint64_t *
             }
     // tmp_c2 (the call): hram | its two counters | z16 | seg_off | tree states | statuses (host form)
     // tmp_d (sized by the largest pass): term scalars | term points | sums | z s | flags of R, of A, of the segments
-    const size_t c_h = al256(n * 64), c_fl = 256, c_z = al256((n + 4) * 16), c_off = al256((m + 1) * 8), c_slot = al256(iv_slot.size() * 2),
-                 c_iv = al256(ivs.size() * 8), c_st = d_status ? 0 : al256(m);
-    const size_t p_sc = al256(R.maxt * 32), p_pt = al256(R.maxt * 160), p_sum = al256(R.max_segs * 160), p_zs = al256(R.max_sigs * 40),
-                 p_f = al256(R.max_sigs), p_sf = al256(R.max_segs);
-    if ((r = ctx_reserve(ctx, ctx->tmp_c2, c_h + c_fl + c_z + c_off + c_slot + c_iv + c_st + 256)) ||
-        (r = ctx_reserve(ctx, ctx->tmp_d, p_sc + p_pt + p_sum + p_zs + 2 * p_f + p_sf + 256)))
-        return r;
-    uint8_t *cb = (uint8_t *)ctx->tmp_c2.p, *pb = (uint8_t *)ctx->tmp_d.p;
-    uint8_t *hram = cb, *z16 = cb + c_h + c_fl;
-    uint32_t *hfl = (uint32_t *)(cb + c_h);
-    uint64_t *d_off = (uint64_t *)(z16 + c_z);
-    uint16_t *d_slot = (uint16_t *)((uint8_t *)d_off + c_off);
-    uint64_t *d_ivs = (uint64_t *)((uint8_t *)d_slot + c_slot);
-    uint8_t *status = d_status ? d_status : (uint8_t *)d_ivs + c_iv;
-    uint8_t *scal = pb, *pts = scal + p_sc, *sums = pts + p_pt, *fl_r = sums + p_sum + p_zs, *fl_a = fl_r + p_f, *seg_fl = fl_a + p_f;
-    uint32_t *zs = (uint32_t *)(sums + p_sum);
+    ws_layout C, P;
+    const size_t c_h = C.part(n * 64), c_fl = C.part(256), c_z = C.part((n + 4) * 16), c_off = C.part((m + 1) * 8), c_slot = C.part(iv_slot.size() * 2),
+                 c_iv = C.part(ivs.size() * 8), c_st = C.part(d_status ? 0 : m);
+    const size_t p_sc = P.part(R.maxt * 32), p_pt = P.part(R.maxt * 160), p_sum = P.part(R.max_segs * 160), p_zs = P.part(R.max_sigs * 40),
+                 p_fr = P.part(R.max_sigs), p_fa = P.part(R.max_sigs), p_sf = P.part(R.max_segs);
+    if ((r = C.reserve(ctx, ctx->tmp_c2, 256)) || (r = P.reserve(ctx, ctx->tmp_d, 256))) return r;
+    uint8_t *hram = C.at(c_h), *z16 = C.at(c_z), *status = d_status ? d_status : C.at(c_st);
+    uint32_t *hfl = C.at<uint32_t>(c_fl);
+    uint64_t *d_off = C.at<uint64_t>(c_off), *d_ivs = C.at<uint64_t>(c_iv);
+    uint16_t *d_slot = C.at<uint16_t>(c_slot);
+    uint8_t *scal = P.at(p_sc), *pts = P.at(p_pt), *sums = P.at(p_sum), *fl_r = P.at(p_fr), *fl_a = P.at(p_fa), *seg_fl = P.at(p_sf);
+    uint32_t *zs = P.at<uint32_t>(p_zs);
     uint32_t h_fl[2] = {0, 0};
     std::vector<uint64_t> toff;
     auto enqueue = [&]() -> int32_t {
